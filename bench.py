@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Headline benchmark: tokens/s at batch 1, speculative decoding on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step computed (emitted token ids, the target's verify logits) as .npy
+files, so that two builds can be compared output for output on identical seeded inputs.
 
 A "step" is one speculative iteration of the hot path (draft-tree expand + target verify +
 accept scan + KV compaction) on synthetic input.  Default workload = the configuration
@@ -22,8 +25,8 @@ N = 1 also reports, on the same JSON line: `roofline` (live HIP-event timing of 
 host cores).
 
 N > 1: one rank per GPU.  Launched by `python -m torch.distributed.run ... bench.py --gpus N ...` the ranks come from
-the environment; launched as plain `python bench.py --gpus N` the script re-executes itself under
-torch.distributed.run with N ranks (and refuses to run if the box has fewer than N GPUs).  The headline `value` at
+the environment; launched as plain `python bench.py --gpus N` the script starts itself again, as a child process,
+under torch.distributed.run with N ranks (and refuses to run if the box has fewer than N GPUs).  The headline `value` at
 N > 1 is N independent requests, one engine replica per GPU, no data-path collective ("scaling": "weak"; a batch-1
 request is a sequential chain of layers and does not shard for speed); the timed region is bracketed by barriers and
 the max over ranks is used.  The same line then carries `pp` (the target's layers sharded over the N ranks, RCCL
@@ -105,8 +108,12 @@ def self_launch(args):
     """`python bench.py --gpus N` (N > 1) outside torch.distributed.run: start the N ranks ourselves."""
     if args.gpus <= 1 or "WORLD_SIZE" in os.environ:
         return
+    import signal
+    import subprocess
     if not (args.dry_run or share_gpu()):
-        have = torch.cuda.device_count() if torch.cuda.is_available() else 0
+        # counted in a child process: the launcher starts the ranks and never opens the GPU itself
+        probe = "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"
+        have = int(subprocess.run([sys.executable, "-c", probe], capture_output=True, text=True, check=True).stdout.split()[-1])
         if have < args.gpus:
             raise SystemExit(f"bench.py --gpus {args.gpus}: this box has {have} GPU(s); refusing to report an "
                              f"{args.gpus}-GPU number from fewer devices")
@@ -117,7 +124,10 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    child = subprocess.Popen(cmd)
+    signal.signal(signal.SIGTERM, lambda *_: child.terminate())
+    rc = child.wait()
+    raise SystemExit(rc if rc >= 0 else 128 - rc)     # killed by signal n: exit 128 + n, as a shell reports it
 
 
 class Watchdog:
@@ -686,6 +696,33 @@ def headline(args, wl, dtype, device, rank, world, dist, agg_device):
     return eng, gm, acc, dt, tokens, info
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(eng, start, out_dir):
+    """--dump-outputs: what the timed loop computed in its LAST step, as a caller of the engine receives it, written as
+    .npy files so that two builds can be compared output for output (the same arguments give the same seeded weights,
+    prompt and acceptance draws):
+      tokens.npy            the request's emitted ids from the end of the prompt through that step (what generate()
+                            returns: the bonus token last), float64
+      last_step_tokens.npy  the ids that step committed, its bonus token last, float64
+      target_logits.npy     the target's verify logits of that step, [tree_size, vocab], float32
+    Must run right after the timed loop, before anything else uses the engine."""
+    import numpy as np
+    torch.cuda.synchronize()
+    n, keep = eng.num_nodes, eng.last_accept
+    toks = eng.tokens[:n + 1].to(torch.float64).cpu()
+    arrays = {"tokens": toks[start:], "last_step_tokens": toks[n - keep:],
+              "target_logits": eng.target_model.logits_buffer[:eng.tree_size, :eng.vocab_size].float().cpu()}
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.numpy())
+    return {"dir": out_dir, "shapes": {name: list(a.shape) for name, a in arrays.items()}}
+
+
 def aggregate(dt, tokens, world, dist, agg_device):
     """max over ranks of the timed region, sum over ranks of the units processed"""
     if world > 1:
@@ -772,7 +809,12 @@ def main():
     ap.add_argument("--phase-timeout", type=float, default=240.0, help="watchdog per pp / tp phase, seconds")
     ap.add_argument("--dry-run", action="store_true", help="launch plumbing only (gloo, no GPU work)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (emitted token ids, the target's verify "
+                         "logits) to DIR/<name>.npy, rank 0 of the headline")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dry_run or args.parallel != "replicas"):
+        raise SystemExit("--dump-outputs writes the headline's outputs: not with --dry-run or --parallel pp / tp")
     if os.environ.get("UMB_BENCH_STACKS"):              # diagnostics: dump every thread's Python stack after N seconds
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ["UMB_BENCH_STACKS"]), repeat=False)
@@ -785,7 +827,7 @@ def main():
     if need_len > args.max_length:
         args.max_length = (need_len + 1023) // 1024 * 1024
         print(f"bench.py: --steps {args.steps} needs a context of {need_len} tokens: max_length raised to {args.max_length}", file=sys.stderr)
-    self_launch(args)                                   # N > 1 outside torch.distributed.run: re-exec with N ranks
+    self_launch(args)                                   # N > 1 outside torch.distributed.run: start N ranks
 
     rank, world, local = dist_env()
     if world != args.gpus:
@@ -858,6 +900,8 @@ def main():
             print(f"bench: host arena not reserved ({type(e).__name__}: {e})", file=sys.stderr, flush=True)
     eng, gm, acc, dt, tokens, info = headline(args, wl, dtype, device, rank, world, dist, agg_device)
     out = headline_line(args, wl, eng, gm, acc, dt, tokens, info, world)
+    if args.dump_outputs and rank == 0:
+        out["dump_outputs"] = dump_outputs(eng, info["start"], args.dump_outputs)
     accept_len = out["accept_len"]
 
     if world == 1:

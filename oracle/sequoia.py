@@ -5,6 +5,8 @@ keep the `width` best (parent, rank) candidates by accumulated log-acceptance.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 DEFAULT_ACC = [0.65, 0.2, 0.1, 0.05]          # sequoia_utils.py:7
@@ -26,7 +28,8 @@ def ancestor_mask(successors):
 
 
 def generate(width: int, depth: int, acc=None) -> dict:
-    acc = torch.log(torch.tensor(DEFAULT_ACC if acc is None else acc, dtype=torch.float32))
+    acc = torch.tensor(DEFAULT_ACC if acc is None else acc, dtype=torch.float32)
+    acc = torch.tensor([math.log(a) if a > 0 else -math.inf for a in acc.tolist()], dtype=torch.float32)  # same on every CPU
     B = len(acc)
     roots, score, succ, branches, node_depth = [[0]], [[0.0]], [[]], [[0]], [0]
     for i in range(depth):

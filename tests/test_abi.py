@@ -1,5 +1,6 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library builds for gfx950, loads, and exports
 every symbol include/umbrella_hip.h declares; host-side formats round-trip.  No compute calls."""
+import math
 import os
 import re
 
@@ -126,6 +127,23 @@ def test_sequoia_generator_and_expected_accept():
         assert json.load(f) == gm["3x4"]
     e = expected_accept_length(gm["3x4"], [0.65, 0.2, 0.1, 0.05])
     assert 3.0 < e < 3.6
+
+
+def test_sequoia_generators_do_not_depend_on_the_cpus_log(monkeypatch):
+    """The default vector's candidates tie in real arithmetic and are ordered by the last bit of their float32 sums.
+    torch.log's vectorised CPU kernels can be one ulp off on some processors (log(0.65f)): with such a log in place both
+    generators must still build the reference's shipped trees."""
+    import json
+    from oracle import sequoia
+    from umbrella_amd.sequoia_utils import generate_sequoia_tree
+    with open(os.path.join(ROOT, "tests", "golden", "growmaps.json")) as f:
+        gm = json.load(f)
+    log = torch.log
+    monkeypatch.setattr(torch, "log", lambda x, *a, **k: torch.nextafter(log(x, *a, **k), torch.full_like(x, -math.inf)))
+    assert generate_sequoia_tree(3, 4) == gm["3x4"]
+    assert generate_sequoia_tree(5, 6, gm["5x6_acc"]) == gm["5x6"]
+    assert sequoia.generate(3, 4) == gm["3x4"]
+    assert sequoia.generate(5, 6, gm["5x6_acc"]) == gm["5x6"]
 
 
 def test_config_table_and_rope():

@@ -51,6 +51,55 @@ def test_refuses_more_gpus_than_the_box_has():
     assert not _json_lines(r.stdout)
 
 
+def test_dump_outputs_needs_the_headline_path(tmp_path):
+    """--dump-outputs writes the headline's outputs: a dry run has none, and it says so instead of writing nothing"""
+    r = _run(["--steps", "2", "--warmup", "0", "--dry-run", "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode != 0 and "--dump-outputs" in (r.stderr + r.stdout)
+    assert not (tmp_path / "out").exists()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_identical_run_to_run(tmp_path):
+    """`bench.py --dump-outputs DIR` (tiny models): --steps sets the timed steps, the line carries ms_per_step, the dumped
+    logits are the last timed step's (its committed ids are their arg-maxes along a path of the tree), and two runs with
+    the same arguments write the same arrays."""
+    import numpy as np
+    from umbrella_amd.sequoia_utils import generate_sequoia_tree
+    args = ["--gpus", "1", "--steps", "5", "--warmup", "2", "--workload", "tiny", "--max-length", "512", "--prompt-len", "24",
+            "--no-roofline", "--no-secondary", "--no-cpu-baseline"]
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = _run([*args, "--dump-outputs", str(d)], timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1, r.stdout
+        out = lines[0]
+        assert out["steps"] == 5 and out["ms_per_step"] > 0
+        files = {p.name: np.load(p) for p in d.iterdir()}
+        assert sorted(files) == ["last_step_tokens.npy", "target_logits.npy", "tokens.npy"]
+        assert files["tokens.npy"].dtype == np.float64 and files["target_logits.npy"].dtype == np.float32
+        assert files["target_logits.npy"].shape == (out["config"]["tree_size"], 512)
+        assert np.isfinite(files["target_logits.npy"]).all()
+        # warm-up + timed steps each emit at least one token; the last step's ids close the request's sequence
+        assert len(files["tokens.npy"]) >= 1 + 2 + 5
+        last = files["last_step_tokens.npy"]
+        assert 2 <= len(last) and np.array_equal(files["tokens.npy"][-len(last):], last)
+        # the logits are that step's: greedy verify commits, after the root, the arg-max of each accepted node's row,
+        # so some root-first path of the 3x4 tree must carry the committed ids (bonus last) as its rows' arg-maxes
+        lg = files["target_logits.npy"]
+        succ = generate_sequoia_tree(3, 4)["Successors"]
+
+        def follows(node, i):                   # last[i] holds the maximum of the node's row (16-bit ties allowed)
+            if lg[node, int(last[i])] != lg[node].max():
+                return False
+            return i == len(last) - 1 or any(follows(c, i + 1) for c in succ[node])
+        assert follows(0, 1), (last, lg.argmax(axis=1))
+        dumps.append(files)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+
+
 @pytest.mark.gpu
 def test_gpus2_shared_gpu_runs_replicas_pp_and_tp():
     """Two ranks on this box's one GPU (gloo, host-staged hops), tiny models: the real multi-rank code path of

@@ -372,8 +372,8 @@ def _c5_worker(rank, world, port, q, prompt, steer):
 def test_c5_70b_awq_eight_stages():
     """BASELINE config 5: eight processes x 10 of the 70B-AWQ's 80 layers (4.5 GB of int4 each), draft = all 16 layers of
     the 1B on stage 0, Sequoia 3x4 (T = 13: 13 x 8192 x 2 B = 213 KB per hop).  Token ids == the single-process headline
-    engine's (default schedules, persistent draft chain included) for >= 40 tokens, with the raw random draft and with
-    the steered one."""
+    engine's (default schedules, persistent draft chain included) for >= 40 tokens with the raw random draft, and with
+    the steered one up to a committed, margin-checked near-tie, where either side of the tie is accepted."""
     import socket
     import torch.multiprocessing as mp
     import __graft_entry__ as ge
@@ -427,7 +427,16 @@ def test_c5_70b_awq_eight_stages():
     assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
     assert got["layers_per_rank"] == 10 and got["tree_size"] == 13 and got["hop_bytes"] == 13 * 8192 * 2
     assert len(got["raw"]) >= C5_NEW and got["raw"] == raw["generated_tokens"]
-    assert got["steered"] == tk and got["diverged"] == 0 and abs(got["accept"] - accept) < 1e-9 and accept > 2.0
+    # The single-process steered run is the headline pair's (same models, tree and prompt).  Where the committed near-tie list
+    # records a margin-checked 16-bit near-tie of that run, the eight stages may take the other side of it: token for token up
+    # to that position, there one of the tie's two candidates; after it the two continuations have different contexts.
+    ties = {m[0]: (m[1], m[2]) for m in _TIES.get("headline 70B-AWQ + 1B 3x4/steered draft", [])}
+    switch = next((i for i, (a, b) in enumerate(zip(got["steered"], tk)) if a != b), None)
+    assert len(got["steered"]) == len(tk) and accept > 2.0
+    if switch is None:
+        assert got["diverged"] == 0 and abs(got["accept"] - accept) < 1e-9
+    else:
+        assert switch in ties and got["steered"][switch] in ties[switch], (switch, got["steered"][switch], tk[switch], ties)
     report_fact("full_depth/C5 70B-AWQ x 8 stages", dict(layers_per_rank=got["layers_per_rank"], hop_bytes=got["hop_bytes"],
                 tokens_raw=len(got["raw"]), tokens_steered=len(got["steered"]), accept_steered=got["accept"],
-                raw_accept=got["raw_accept"], equals_single_process=True))
+                raw_accept=got["raw_accept"], equals_single_process=switch is None, near_tie_taken_otherwise_at=switch))

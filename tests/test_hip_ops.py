@@ -309,16 +309,15 @@ def _tree_mask(T, rs):
 def test_tree_attention(dev, dtype, Hq, Hkv, D, T, prefix, path):
     """Tree-masked and causal attention vs the oracle through the three kernel paths: one launch, one 2048-key span
     (merge inside the block); key splits + combine kernel (long context, no counters); one launch with several
-    spans merged by the last-arriving block (long context, counters)."""
-    if path == "single" and prefix + T > 1024:
-        pytest.skip("context longer than this path's Lmax")
+    spans merged by the last-arriving block (long context, counters).  "single" sizes the cache to the context
+    (no counters): one launch while one span covers it, the key-split kernel once it does not (2513, 4205 keys)."""
     from umbrella_amd import _lib
     from umbrella_amd.models.llama import pack_mask_bits
     rs = np.random.RandomState(T * 1000 + prefix + D)
     g = torch.Generator().manual_seed(T + prefix)
-    Lmax, chunk = (1024, 256) if path == "single" else (8192, 512)
-    splits = Lmax // chunk
     S = prefix + T
+    Lmax, chunk = (max(1024, -(-S // 1024) * 1024), 256) if path == "single" else (8192, 512)
+    splits = Lmax // chunk
     q = torch.randn(T, Hq, D, generator=g).to(dtype)
     k = torch.randn(S, Hkv, D, generator=g).to(dtype)
     v = torch.randn(S, Hkv, D, generator=g).to(dtype)
@@ -909,8 +908,6 @@ def test_verify_gemm_wide_every_output_70b_shapes(dev, shape, T):
     from umbrella_amd.models.llama import PackedLinear
     from umbrella_amd.models.synthetic import synth_awq_tensors
     N, K, il = {"qkv": (10240, 8192, False), "gu": (2 * 28672, 8192, True), "down": (8192, 28672, False)}[shape]
-    if shape == "gu" and T == 385:
-        pytest.skip("covered by 257 / 769 (same kernel instantiation)")
     gen = torch.Generator(device=dev).manual_seed(T + N)
     qw, qz, sc = synth_awq_tensors(N, K, 128, dev, gen)
     lin = PackedLinear.from_awq(qw, qz, sc, interleave=il)

@@ -130,8 +130,6 @@ def test_ll_silu_epilogue(dev, dtype, awq, T):
     layout (llama.py:107-110 behind model_utils.py:54-64)."""
     from umbrella_amd.models.llama import PackedLinear, from_fm
     from umbrella_amd.models.synthetic import synth_awq_tensors
-    if awq and dtype != torch.float16:
-        pytest.skip("AWQ checkpoints are fp16")
     gen = torch.Generator(device=dev).manual_seed(T + awq)
     H, I = 512, 1024
     if awq:
@@ -158,7 +156,7 @@ def test_ll_silu_epilogue(dev, dtype, awq, T):
     y = (hw.float() @ wfull.t()) * inv
     g_, u_ = y[:, :I].to(dtype).float(), y[:, I:].to(dtype).float()
     ref = (torch.nn.functional.silu(g_).to(dtype).float() * u_).to(dtype).float()
-    tol = 3e-3 if awq else 2e-2 if dtype == torch.bfloat16 else 3e-3
+    tol = 2e-2 if dtype == torch.bfloat16 else 3e-3             # bf16 outputs: 8 mantissa bits
     assert _rel(got, ref) < tol, _rel(got, ref)
 
 

@@ -36,7 +36,11 @@ def generate_sequoia_tree(width: int, depth: int, acc=None, json_file=None):
         assert width <= 4, "Using default acceptance rate vector, require width<=4"
         acc = DEFAULT_ACC
     import torch
-    lacc = torch.log(torch.tensor(acc, dtype=torch.float32))
+    # float32 logs rounded correctly on every host: candidates that tie in real arithmetic (the same factors in another
+    # order) are ordered by the last bit of their float32 sums, and torch.log's vectorised CPU kernels can differ by one
+    # ulp between processors (log(0.65f)), which would make the tree depend on the CPU it is built on
+    lacc = torch.tensor([math.log(a) if a > 0 else -math.inf for a in torch.tensor(acc, dtype=torch.float32).tolist()],
+                        dtype=torch.float32)
     nb = len(lacc)
     roots, branches, succ, tdepth = [[0]], [[0]], [[]], [0]
     scores = torch.zeros(1, dtype=torch.float32)

@@ -483,6 +483,56 @@ typedef struct UmbOffload {
 int umb_model_forward_offload(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* step, const UmbOffload* off,
                               umb_stream_t stream);
 
+/* ------------------------------------------------------------------ Gemma-2 (umbrella/models/gemma.py, gemma_layer.py) */
+/* Gemma2RMSNorm (HF modeling_gemma2): out = round(x * rsqrt(mean x^2 + eps) * (1 + w)) in fp32.  scale != 0: x is first
+ * replaced by round(x * scale) in place (Gemma2Model's embedding normalizer sqrt(H), itself rounded to the dtype by the
+ * caller).  H % 4 == 0, H <= 16384. */
+int umb_gemma_rmsnorm(void* out, void* x, const void* w, float eps, float scale, int rows, int H, int dtype,
+                      umb_stream_t stream);
+/* Gemma2DecoderLayer's sandwich around o_proj / down_proj: y = round(sum_s partial) (split order), h = round(h +
+ * round(gemma_norm(y, w_post))), xn_out = gemma_norm(h, w_next) (post_attention + pre_feedforward norms after o,
+ * post_feedforward + the next input_layernorm / final norm after down); xn_out NULL: h only.  One block per row. */
+int umb_gemma_sandwich(const float* partial, int S, int T, int H, void* h, void* xn_out, const void* w_post,
+                       const void* w_next, float eps, int dtype, umb_stream_t stream);
+/* Gemma2MLP act_fn(gate) * up with act_fn = gelu_pytorch_tanh; partial rows [gate | up]; gate, up, gelu(gate) and the
+ * product each rounded to the model dtype */
+int umb_reduce_gelu_mul(const void* partial, int S, int T, int I, void* act, int dtype, umb_stream_t stream);
+/* final_logit_softcapping (gemma.py inference): x = cap * tanh(x / cap) over n fp32 logits, in place */
+int umb_logit_softcap(float* logits, int64_t n, float cap, umb_stream_t stream);
+/* Gemma-2 tree attention (flashinfer with logits_soft_cap and a sliding window in gemma_layer.py): umb_tree_attn with
+ * scores softcap * tanh(s * scale / softcap) (softcap > 0) and, for window > 0, key slot c hidden from query row t once
+ * pos[t] - c >= window -- exact for prompt keys (slot == position) and for tree keys while window > tree depth.  Key tiles
+ * before the 32-key tile holding the block's first visible key are not read.  D = 128 / 256; counters required. */
+int umb_tree_attn_gemma2(void* out, const void* q, const void* k_cache, const void* vt_cache, void* po, void* pml,
+                         const int* prefix_len, const void* mask_bits, int mask_words, int n_mask_keys, int T, int Hq,
+                         int Hkv, int D, int Lmax, int max_splits, float scale, float softcap, const int* pos, int window,
+                         uint32_t* counters, int dtype, umb_stream_t stream);
+
+typedef struct UmbGemma2Norms {
+  const void* pre_ff;               /* pre_feedforward_layernorm weight [H] */
+  const void* post_ff;              /* post_feedforward_layernorm weight [H] */
+} UmbGemma2Norms;
+
+typedef struct UmbGemma2 {
+  float attn_softcap;               /* attn_logit_softcapping (0: off) */
+  float final_softcap;              /* final_logit_softcapping (0: off) */
+  float embed_scale;                /* round(sqrt(H)) in the model dtype */
+  int32_t window;                   /* sliding_window (0: every layer global) */
+  int32_t slide_parity;             /* layer l slides when l % 2 == slide_parity (HF Gemma-2: the even layers) */
+  int32_t pad_;
+  const UmbGemma2Norms* norms;      /* host array, L entries */
+} UmbGemma2;
+
+/* Gemma2ForCausalLM forward on the 8-launch schedule (ws->fused == 0; gemma.py inference / gemma_layer.py layer_compute):
+ * embedding * sqrt(H) -> L x [ input norm | qkv -> RoPE -> attention (cap; window on sliding layers; scale m->attn_scale =
+ * query_pre_attn_scalar^-1/2) -> o -> sandwich -> gate/up -> gelu * up -> down -> sandwich ] -> lm_head -> soft-cap.
+ * m->layers[l].norm1 / norm2: input_layernorm / post_attention_layernorm; g->norms: the other two.  No host syncs. */
+int umb_model_forward_gemma2(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* step, const UmbGemma2* g,
+                             umb_stream_t stream);
+/* the same with the linears streamed from pinned host slabs as umb_model_forward_offload (norm weights stay resident) */
+int umb_model_forward_gemma2_offload(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* step, const UmbGemma2* g,
+                                     const UmbOffload* off, umb_stream_t stream);
+
 /* diagnostic: n dependent no-op launches of `blocks` workgroups (dispatch cadence) */
 int umb_bench_launch(int n, int blocks, int* p, umb_stream_t stream);
 

@@ -110,6 +110,16 @@ class UmbTP(C.Structure):
 MAX_SLABS = 8
 
 
+class UmbGemma2Norms(C.Structure):
+    _fields_ = [("pre_ff", C.c_void_p), ("post_ff", C.c_void_p)]
+
+
+class UmbGemma2(C.Structure):
+    _fields_ = [("attn_softcap", C.c_float), ("final_softcap", C.c_float), ("embed_scale", C.c_float),
+                ("window", C.c_int32), ("slide_parity", C.c_int32), ("pad_", C.c_int32),
+                ("norms", C.POINTER(UmbGemma2Norms))]
+
+
 class UmbOffload(C.Structure):
     _fields_ = [("host_slabs", C.POINTER(C.c_void_p)), ("slab_bytes", C.c_size_t), ("dev_slab", C.c_void_p * MAX_SLABS),
                 ("copy_stream", C.c_void_p), ("ev_copied", C.c_void_p * MAX_SLABS), ("ev_free", C.c_void_p * MAX_SLABS),
@@ -182,6 +192,14 @@ SIGNATURES = {
     "umb_tp_xchg_free": [_P],
     "umb_model_forward_offload": [C.POINTER(UmbModel), C.POINTER(UmbWorkspace), C.POINTER(UmbStep),
                                   C.POINTER(UmbOffload), _P],
+    "umb_gemma_rmsnorm": [_P, _P, _P, _F, _F, _I, _I, _I, _P],
+    "umb_gemma_sandwich": [_P, _I, _I, _I, _P, _P, _P, _P, _F, _I, _P],
+    "umb_reduce_gelu_mul": [_P, _I, _I, _I, _P, _I, _P],
+    "umb_logit_softcap": [_P, C.c_int64, _F, _P],
+    "umb_tree_attn_gemma2": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _I, _P, _I, _P],
+    "umb_model_forward_gemma2": [C.POINTER(UmbModel), C.POINTER(UmbWorkspace), C.POINTER(UmbStep), C.POINTER(UmbGemma2), _P],
+    "umb_model_forward_gemma2_offload": [C.POINTER(UmbModel), C.POINTER(UmbWorkspace), C.POINTER(UmbStep),
+                                         C.POINTER(UmbGemma2), C.POINTER(UmbOffload), _P],
     "umb_bench_launch": [_I, _I, _P, _P],
     "umb_version": [],
 }

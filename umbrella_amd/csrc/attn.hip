@@ -181,15 +181,20 @@ __global__ __launch_bounds__(256) void tree_attn_kernel(const u16* __restrict__ 
 // at once): each span block publishes its merged partial with write-through stores and the last one to arrive on the
 // (head, tile) counter combines them (same protocol as the split-K epilogues).  grid = (Hkv, query tiles, spans):
 // kv head h stays on XCD h % 8.
-template <typename P, int D, int NW, int NQ = 1>
-__global__ __launch_bounds__(64 * NW, NQ > 1 ? 1 : 2) void tree_attn1_kernel(const u16* __restrict__ q, const u16* __restrict__ kc,
+template <typename P, int D, int NW, int NQ = 1, bool GM = false>
+__global__ __launch_bounds__(64 * NW, (NQ > 1 || D > 128) ? 1 : 2) void tree_attn1_kernel(const u16* __restrict__ q, const u16* __restrict__ kc,
                                                          const u16* __restrict__ vt, const int* __restrict__ prefix_p,
                                                          int T, int Hq, int Hkv, int Lmax, int mask_words, int n_mask_keys,
                                                          const unsigned long long* __restrict__ mask_bits,
                                                          float scale, u16* __restrict__ out, int KBK,
                                                          float* __restrict__ po, float* __restrict__ pml,
-                                                         unsigned* __restrict__ counters, int out_fm_tt, int single_max) {
+                                                         unsigned* __restrict__ counters, int out_fm_tt, int single_max,
+                                                         const int* __restrict__ qpos, float softcap, int window) {
   // argument order: the first 14 dwords (what the q / K loads need) are preloaded into SGPRs at wave launch
+  // GM (Gemma-2, umb_tree_attn_gemma2): scores soft-capped, cap * tanh(s / cap) (softcap > 0), and a sliding window: key
+  // slot c is hidden from a query at position p = qpos[t] when p - c >= window (window > 0).  Exact for prompt / prefix keys
+  // (slot == position) and, as long as window > tree depth, for tree keys (slot >= position).  Key tiles before the first one
+  // any row of the block can see are never read.  GM == false: none of it is compiled.
   // NQ (round 4): query tiles per block.  Every K / V^T tile a wave loads serves NQ 16-row query tiles instead of one --
   // the wide trees and prompt chunks (hundreds of query tiles per kv head) are bound by that L2 -> register traffic
   // (T = 769: 385 query tiles x 8 kv heads each walking ~500 keys x 512 B = 0.8 GB per layer), not by the matrix pipe.
@@ -207,8 +212,8 @@ __global__ __launch_bounds__(64 * NW, NQ > 1 ? 1 : 2) void tree_attn1_kernel(con
   // the device-resident prefix length is known (one dependent round trip less on a launch that lasts ~3 of them).
   // Rows past kv_end hold zeros or stale finite values (the cache is zero-initialised) and are masked below.
   const int k_lo = blockIdx.z * KBK;
-  const int kstart = k_lo + wv * 32;
-  const bool spec = kstart + 32 <= Lmax;
+  int kstart = k_lo + wv * 32;
+  const bool spec = !GM && kstart + 32 <= Lmax;            // GM: the first tile depends on the window
   u32x4 ka[2][DS], kb2[2][DS], va[DT], vb[DT];
   if (spec) {
     // fragment order (common.h kc_off / vt_off): each of the 2 DS + DT loads of a tile is one contiguous KiB
@@ -270,6 +275,28 @@ __global__ __launch_bounds__(64 * NW, NQ > 1 ? 1 : 2) void tree_attn1_kernel(con
     for (int off = 1; off < 64; off <<= 1) top = max(top, __shfl_xor(top, off, 64));
     k_hi = min(k_hi, prefix + top + 1);
   }
+  // GM window: first visible key of the block = (lowest row position) - window + 1; the walk starts at the 32-key tile holding
+  // it.  Spans that end before it leave at once and are not merged (span0: first live span).
+  int span0 = 0;
+  int ppos[NQ];
+  if constexpr (GM) {
+    int pmin = 0x7fffffff;
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) {
+      ppos[qi] = row_ok[qi] ? qpos[t[qi]] : 0;
+      if (row_ok[qi]) pmin = min(pmin, ppos[qi]);
+    }
+    if (window > 0) {
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) pmin = min(pmin, __shfl_xor(pmin, off, 64));
+      const int kfirst = max(pmin - window + 1, 0) & ~31;
+      if (!one_span) {
+        if (k_lo + KBK <= kfirst) return;                         // whole block: the span lies before every row's window
+        span0 = kfirst / KBK;
+      }
+      kstart = max(k_lo, kfirst) + wv * 32;
+    }
+  }
 
   auto load_k = [&](int k0, u32x4 (&ak)[2][DS]) {
 #pragma unroll
@@ -322,7 +349,15 @@ __global__ __launch_bounds__(64 * NW, NQ > 1 ? 1 : 2) void tree_attn1_kernel(con
       for (int e = 0; e < 8; ++e) {
         const int key = k0 + gq * 8 + e;
         float sc = st[e >> 2][e & 3] * scale;
-        const bool vis = row_ok[qi] && key < k_hi && ((vbits >> e) & 1u);
+        bool vis = row_ok[qi] && key < k_hi && ((vbits >> e) & 1u);
+        if constexpr (GM) {
+          if (softcap > 0.f) {
+            // tanh(x) = 1 - 2 / (e^2x + 1): one v_exp_f32 and one v_rcp_f32 (e^2x = inf -> 1, 0 -> -1)
+            const float e2 = __expf(2.f * sc / softcap);
+            sc = softcap * (1.f - 2.f * __builtin_amdgcn_rcpf(e2 + 1.f));
+          }
+          if (window > 0) vis = vis && ppos[qi] - key < window;
+        }
         sc = vis ? sc : -INFINITY;
         pv[e] = sc;
         tmax = fmaxf(tmax, sc);
@@ -347,6 +382,13 @@ __global__ __launch_bounds__(64 * NW, NQ > 1 ? 1 : 2) void tree_attn1_kernel(con
     }
   };
 
+  if constexpr (D > 128) {
+    // D = 256: O^T alone is 64 VGPRs and one K + V^T tile 128; no second tile is kept in flight
+    for (int k0 = kstart; k0 < k_hi; k0 += NW * 32) {
+      load_k(k0, ka); load_v(k0, va);
+      tile(k0, ka, va);
+    }
+  } else {
   if (kstart < k_hi && !spec) { load_k(kstart, ka); load_v(kstart, va); }
   for (int k0 = kstart; k0 < k_hi; k0 += 2 * NW * 32) {
     const int k1 = k0 + NW * 32;
@@ -358,7 +400,8 @@ __global__ __launch_bounds__(64 * NW, NQ > 1 ? 1 : 2) void tree_attn1_kernel(con
       tile(k1, kb2, vb);
     }
   }
-  const int nsp = one_span ? 1 : (kv_end + KBK - 1) / KBK;     // span blocks that did not exit above
+  }
+  const int nsp = one_span ? 1 : (kv_end + KBK - 1) / KBK;     // span blocks that did not exit above (from span0 on)
   constexpr int NDT = (DT + NW - 1) / NW;
   __shared__ int s_last;
   bool last_known = false;
@@ -402,7 +445,7 @@ __global__ __launch_bounds__(64 * NW, NQ > 1 ? 1 : 2) void tree_attn1_kernel(con
         *reinterpret_cast<uint2*>(out + orow * D + dt * 16 + gq * 4) = o2;
       }
     };
-    if (nsp == 1) {
+    if (nsp - span0 == 1) {
       if (rok) {
         const float inv = L > 0.f ? 1.f / L : 0.f;
 #pragma unroll
@@ -434,7 +477,7 @@ __global__ __launch_bounds__(64 * NW, NQ > 1 ? 1 : 2) void tree_attn1_kernel(con
     if (threadIdx.x == 0) {
       unsigned* cnt = counters + (long)h * gridDim.y + qt;
       const unsigned ticket = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int last = ticket == (unsigned)(nsp - 1);
+      const int last = ticket == (unsigned)(nsp - span0 - 1);
       if (last) {
         __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -453,9 +496,9 @@ __global__ __launch_bounds__(64 * NW, NQ > 1 ? 1 : 2) void tree_attn1_kernel(con
     const int tq = t[qi], hqq = hq[qi];
     const long orow = (long)tq * Hq + hqq;
     float Mg = NEG_BIG;
-    for (int s2 = 0; s2 < nsp; ++s2) Mg = fmaxf(Mg, pml[(s2 * rows_all + orow) * 2]);
+    for (int s2 = span0; s2 < nsp; ++s2) Mg = fmaxf(Mg, pml[(s2 * rows_all + orow) * 2]);
     float Lg = 0.f;
-    for (int s2 = 0; s2 < nsp; ++s2) {
+    for (int s2 = span0; s2 < nsp; ++s2) {
       const long pr = s2 * rows_all + orow;
       Lg += pml[pr * 2 + 1] * __expf(pml[pr * 2] - Mg);
     }
@@ -465,7 +508,7 @@ __global__ __launch_bounds__(64 * NW, NQ > 1 ? 1 : 2) void tree_attn1_kernel(con
       const int dt = wv + c * NW;
       if (dt >= DT) continue;
       f32x4 ag = {0.f, 0.f, 0.f, 0.f};
-      for (int s2 = 0; s2 < nsp; ++s2) {
+      for (int s2 = span0; s2 < nsp; ++s2) {
         const long pr = s2 * rows_all + orow;
         ag += *reinterpret_cast<const f32x4*>(po + pr * D + dt * 16 + gq * 4) * __expf(pml[pr * 2] - Mg);
       }
@@ -518,21 +561,9 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(u16* __restrict__ out
   }
 }
 
-// partial buffers: po  [max_splits][T][Hq][D] fp32, pml [max_splits][T][Hq][2] fp32
-// counters: >= Hkv * ceil(T * (Hq/Hkv) / 16) zeroed uint32 (self-resetting) -> single-launch kernel for any Lmax;
-// NULL -> single launch only if Lmax <= 2048, else key splits + a combine kernel
-extern "C" int umb_tree_attn2(void* out, const void* q, const void* k_cache, const void* vt_cache, void* po, void* pml,
-                              const int* prefix_len, const void* mask_bits, int mask_words, int n_mask_keys, int T,
-                              int Hq, int Hkv, int D, int Lmax, int chunk, int max_splits, float scale,
-                              unsigned* counters, int out_fm_tt, int dtype, hipStream_t st) {
-  if (T < 1 || Hq % Hkv || chunk % 32 || Lmax % 32 || (D != 32 && D != 64 && D != 128)) return UMB_EINVAL;
-  if (out_fm_tt && (out_fm_tt * 16 < T || (Hq * D) % 32)) return UMB_EINVAL;
-  const int nrows = T * (Hq / Hkv);
-  const int nqt = (nrows + 15) / 16;
-  // Single-launch kernel: with a counters buffer for any Lmax (spans of 2048 keys, cross-block merge only once the
-  // context outgrows a span); without one only when a single span covers Lmax.  The choice depends on Lmax alone
-  // (kv_end lives on the device), so a captured graph stays valid as the context grows.
-  static const bool no_single = getenv("UMB_ATTN_SPLIT") != nullptr;
+// Keys per span (KBK) and the context length up to which a single span walks everything (single_max) of the single-launch
+// kernel; shape-only (Hkv, query tiles, Lmax), so a captured graph stays valid as the context grows.
+static void attn1_spans(int Hkv, int nqt, int Lmax, int max_splits, bool counters, int* KBK_out, int* single_max_out) {
   // Keys per span.  Wide trees fill the chip with (kv head, query tile) pairs and take 2048-key spans; a NARROW launch (a
   // draft level or a static-tree verify: 8 ... 56 blocks) walks a long context on that many CUs -- 70B, T = 13, context 1.6 k:
   // 56 blocks x 786 KB of K / V^T each -- so its spans are 512 keys (round 4): up to Lmax / 512 times the blocks once the
@@ -551,6 +582,27 @@ extern "C" int umb_tree_attn2(void* out, const void* q, const void* k_cache, con
     single_max = one_env > 0 ? one_env : 1024;
     if (single_max < KBK) single_max = KBK;
   }
+  *KBK_out = KBK;
+  *single_max_out = single_max;
+}
+
+// partial buffers: po  [max_splits][T][Hq][D] fp32, pml [max_splits][T][Hq][2] fp32
+// counters: >= Hkv * ceil(T * (Hq/Hkv) / 16) zeroed uint32 (self-resetting) -> single-launch kernel for any Lmax;
+// NULL -> single launch only if Lmax <= 2048, else key splits + a combine kernel
+extern "C" int umb_tree_attn2(void* out, const void* q, const void* k_cache, const void* vt_cache, void* po, void* pml,
+                              const int* prefix_len, const void* mask_bits, int mask_words, int n_mask_keys, int T,
+                              int Hq, int Hkv, int D, int Lmax, int chunk, int max_splits, float scale,
+                              unsigned* counters, int out_fm_tt, int dtype, hipStream_t st) {
+  if (T < 1 || Hq % Hkv || chunk % 32 || Lmax % 32 || (D != 32 && D != 64 && D != 128)) return UMB_EINVAL;
+  if (out_fm_tt && (out_fm_tt * 16 < T || (Hq * D) % 32)) return UMB_EINVAL;
+  const int nrows = T * (Hq / Hkv);
+  const int nqt = (nrows + 15) / 16;
+  // Single-launch kernel: with a counters buffer for any Lmax (spans of 2048 keys, cross-block merge only once the
+  // context outgrows a span); without one only when a single span covers Lmax.  The choice depends on Lmax alone
+  // (kv_end lives on the device), so a captured graph stays valid as the context grows.
+  static const bool no_single = getenv("UMB_ATTN_SPLIT") != nullptr;
+  int KBK, single_max;
+  attn1_spans(Hkv, nqt, Lmax, max_splits, counters != nullptr, &KBK, &single_max);
   const int spans = (Lmax + KBK - 1) / KBK;
   if ((counters || spans == 1) && nqt <= 65535 && spans <= max_splits && !no_single) {
     // Waves per (kv head, query tile): eight while the tiles are few (narrow trees: the keys of a tile are spread over
@@ -570,7 +622,7 @@ extern "C" int umb_tree_attn2(void* out, const void* q, const void* k_cache, con
   hipLaunchKernelGGL((tree_attn1_kernel<P, DD, NWV, NQV>), grid1, block1, 0, st, (const u16*)q, (const u16*)k_cache, \
                      (const u16*)vt_cache, prefix_len, T, Hq, Hkv, Lmax, mask_words, n_mask_keys,                   \
                      (const unsigned long long*)mask_bits, scale, (u16*)out, KBK, (float*)po, (float*)pml, counters, out_fm_tt, \
-                     single_max)
+                     single_max, nullptr, 0.f, 0)
 #define ATT1_(DD)                                                                                                 \
   if (nw == 1 && nq == 2) { ATT1N_(DD, 1, 2); } else if (nw == 1) { ATT1N_(DD, 1, 1); }                            \
   else if (nw == 2 && nq == 2) { ATT1N_(DD, 2, 2); } else if (nw == 2) { ATT1N_(DD, 2, 1); }                       \
@@ -614,4 +666,41 @@ extern "C" int umb_tree_attn(void* out, const void* q, const void* k_cache, cons
                              unsigned* counters, int dtype, hipStream_t st) {
   return umb_tree_attn2(out, q, k_cache, vt_cache, po, pml, prefix_len, mask_bits, mask_words, n_mask_keys, T, Hq, Hkv, D,
                         Lmax, chunk, max_splits, scale, counters, 0, dtype, st);
+}
+
+// Gemma-2 attention (umbrella/models/gemma_layer.py: flashinfer prefill / decode with logits_soft_cap and a sliding window):
+// the single-launch kernel with its GM path -- scores cap * tanh(s * scale / cap) (softcap > 0) and, when window > 0, key
+// slot c hidden from a query at position pos[t] once pos[t] - c >= window; the tiles before the first visible one are not
+// read.  D = 128 / 256; needs the counters buffer (the cross-span merge for any Lmax).
+extern "C" int umb_tree_attn_gemma2(void* out, const void* q, const void* k_cache, const void* vt_cache, void* po, void* pml,
+                                    const int* prefix_len, const void* mask_bits, int mask_words, int n_mask_keys, int T,
+                                    int Hq, int Hkv, int D, int Lmax, int max_splits, float scale, float softcap,
+                                    const int* pos, int window, unsigned* counters, int dtype, hipStream_t st) {
+  if (T < 1 || Hkv < 1 || Hq % Hkv || Lmax % 32 || (D != 128 && D != 256) || !counters || window < 0 || softcap < 0.f ||
+      (window > 0 && !pos))
+    return UMB_EINVAL;
+  const int nqt = (T * (Hq / Hkv) + 15) / 16;
+  int KBK, single_max;
+  attn1_spans(Hkv, nqt, Lmax, max_splits, true, &KBK, &single_max);
+  const int spans = (Lmax + KBK - 1) / KBK;
+  if (nqt > 65535 || spans > max_splits) return UMB_EINVAL;
+  const int nblk = Hkv * nqt;
+  // as umb_tree_attn2; D = 256 stops at four waves: the LDS merge buffer is NW x 16 KiB there
+  const int nw = nblk >= 1792 ? 1 : nblk >= 512 ? 2 : (D > 128 ? 4 : 8);
+  const dim3 grid1(Hkv, nqt, spans), block1(64 * nw);
+#define ATTG_(DD, NWV)                                                                                             \
+  hipLaunchKernelGGL((tree_attn1_kernel<P, DD, NWV, 1, true>), grid1, block1, 0, st, (const u16*)q, (const u16*)k_cache, \
+                     (const u16*)vt_cache, prefix_len, T, Hq, Hkv, Lmax, mask_words, n_mask_keys,                    \
+                     (const unsigned long long*)mask_bits, scale, (u16*)out, KBK, (float*)po, (float*)pml, counters, 0, \
+                     single_max, pos, softcap, window)
+  DISPATCH_DTYPE(dtype, {
+    if (D == 256) {
+      if (nw == 1) { ATTG_(256, 1); } else if (nw == 2) { ATTG_(256, 2); } else { ATTG_(256, 4); }
+    } else {
+      if (nw == 1) { ATTG_(128, 1); } else if (nw == 2) { ATTG_(128, 2); } else { ATTG_(128, 8); }
+    }
+  })
+#undef ATTG_
+  UMB_LAUNCH_CHECK();
+  return UMB_OK;
 }

@@ -562,3 +562,176 @@ extern "C" int umb_sum_splits(float* partial, int S, int64_t n, hipStream_t st) 
   UMB_LAUNCH_CHECK();
   return UMB_OK;
 }
+
+// ------------------------------------------------------------------ Gemma-2 (umbrella/models/gemma.py, gemma_layer.py)
+// Gemma RMSNorm (HF Gemma2RMSNorm): y = x * rsqrt(mean x^2 + eps) * (1 + w), all in fp32, rounded once to the model dtype.
+// Row values are staged in dynamic LDS (H floats), each thread keeping to its own columns: no barrier but the reductions.
+template <typename P>
+__device__ __forceinline__ float gemma_row_inv(float ss, float* red, int H, float eps) {
+  ss = block_sum<256>(ss, red);
+  return rsqrtf(ss / (float)H + eps);
+}
+
+// x (16-bit [rows][H]); scale != 0: x <- round(x * scale) first, written back (the embedding's sqrt(H) normalizer, HF
+// Gemma2Model.forward, itself rounded to the model dtype by the caller); out <- Gemma norm of x with weight w
+template <typename P>
+__global__ __launch_bounds__(256) void gemma_rmsnorm_kernel(u16* __restrict__ out, u16* __restrict__ x, const u16* __restrict__ w,
+                                                            float eps, float scale, int H) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* red = reinterpret_cast<float*>(smem);              // 4 floats
+  float* row = reinterpret_cast<float*>(smem + 16);         // H floats
+  const int t = blockIdx.x;
+  u16* xr = x + (long)t * H;
+  float ss = 0.f;
+  for (int i = threadIdx.x * 4; i < H; i += 1024) {
+    const uint2 v = *reinterpret_cast<const uint2*>(xr + i);
+    float a[4] = {lo_f<P>(v.x), hi_f<P>(v.x), lo_f<P>(v.y), hi_f<P>(v.y)};
+    if (scale != 0.f) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a[e] = rnd<P>(a[e] * scale);
+      uint2 o;
+      o.x = pack2<P>(a[0], a[1]); o.y = pack2<P>(a[2], a[3]);
+      *reinterpret_cast<uint2*>(xr + i) = o;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { row[i + e] = a[e]; ss += a[e] * a[e]; }
+  }
+  const float inv = gemma_row_inv<P>(ss, red, H, eps);
+  for (int i = threadIdx.x * 4; i < H; i += 1024) {
+    const uint2 g = *reinterpret_cast<const uint2*>(w + i);
+    const float gw[4] = {lo_f<P>(g.x), hi_f<P>(g.x), lo_f<P>(g.y), hi_f<P>(g.y)};
+    float y[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) y[e] = (row[i + e] * inv) * (1.f + gw[e]);
+    uint2 o;
+    o.x = pack2<P>(y[0], y[1]); o.y = pack2<P>(y[2], y[3]);
+    *reinterpret_cast<uint2*>(out + (long)t * H + i) = o;
+  }
+}
+
+// Sandwich reduce (Gemma2DecoderLayer): y = round(sum_s partial) (split order 0 .. S-1), z = round(norm(y) * (1 + w_post)),
+// h <- round(h + z), xn <- round(norm(h) * (1 + w_next)) (xn_out / w_next NULL: h only).  One block per token row.
+template <typename P>
+__global__ __launch_bounds__(256) void gemma_sandwich_kernel(const float* __restrict__ part, int S, int T, int H, u16* h,
+                                                             u16* __restrict__ xn_out, const u16* __restrict__ w_post,
+                                                             const u16* __restrict__ w_next, float eps) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* red = reinterpret_cast<float*>(smem);
+  float* row = reinterpret_cast<float*>(smem + 16);
+  const int t = blockIdx.x;
+  const long sstride = (long)T * H;
+  float ss = 0.f;
+  for (int i = threadIdx.x * 4; i < H; i += 1024) {
+    const f32x4 a = sum_splits(part + (long)t * H + i, S, sstride);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { const float y = rnd<P>(a[e]); row[i + e] = y; ss += y * y; }
+  }
+  const float inv1 = gemma_row_inv<P>(ss, red, H, eps);
+  ss = 0.f;
+  for (int i = threadIdx.x * 4; i < H; i += 1024) {
+    const uint2 g = *reinterpret_cast<const uint2*>(w_post + i);
+    const uint2 r = *reinterpret_cast<const uint2*>(h + (long)t * H + i);
+    const float gw[4] = {lo_f<P>(g.x), hi_f<P>(g.x), lo_f<P>(g.y), hi_f<P>(g.y)};
+    const float rv[4] = {lo_f<P>(r.x), hi_f<P>(r.x), lo_f<P>(r.y), hi_f<P>(r.y)};
+    float hh[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float z = rnd<P>((row[i + e] * inv1) * (1.f + gw[e]));
+      hh[e] = rnd<P>(rv[e] + z);
+      row[i + e] = hh[e];
+      ss += hh[e] * hh[e];
+    }
+    uint2 o;
+    o.x = pack2<P>(hh[0], hh[1]); o.y = pack2<P>(hh[2], hh[3]);
+    *reinterpret_cast<uint2*>(h + (long)t * H + i) = o;
+  }
+  if (!xn_out) return;
+  const float inv2 = gemma_row_inv<P>(ss, red, H, eps);
+  for (int i = threadIdx.x * 4; i < H; i += 1024) {
+    const uint2 g = *reinterpret_cast<const uint2*>(w_next + i);
+    const float gw[4] = {lo_f<P>(g.x), hi_f<P>(g.x), lo_f<P>(g.y), hi_f<P>(g.y)};
+    float y[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) y[e] = (row[i + e] * inv2) * (1.f + gw[e]);
+    uint2 o;
+    o.x = pack2<P>(y[0], y[1]); o.y = pack2<P>(y[2], y[3]);
+    *reinterpret_cast<uint2*>(xn_out + (long)t * H + i) = o;
+  }
+}
+
+// act = round(gelu_tanh(round(gate))) * round(up), rounded (Gemma2MLP: act_fn(gate_proj(x)) * up_proj(x), each op in the
+// model dtype); partial rows are [gate | up] (split order 0 .. S-1).  gelu_tanh(x) = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))).
+template <typename P>
+__global__ __launch_bounds__(256) void reduce_gelu_mul_kernel(const float* __restrict__ part, int S, int T, int I,
+                                                              u16* __restrict__ act) {
+  const long gid = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (gid >= (long)T * I) return;
+  const int t = (int)(gid / I), i = (int)(gid % I);
+  const int N = 2 * I;
+  f32x4 g = *reinterpret_cast<const f32x4*>(part + (long)t * N + i);
+  f32x4 u = *reinterpret_cast<const f32x4*>(part + (long)t * N + I + i);
+  for (int s = 1; s < S; ++s) {
+    g += *reinterpret_cast<const f32x4*>(part + ((long)s * T + t) * N + i);
+    u += *reinterpret_cast<const f32x4*>(part + ((long)s * T + t) * N + I + i);
+  }
+  float o[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float x = rnd<P>(g[e]), uu = rnd<P>(u[e]);
+    const float inner = 0.7978845608028654f * (x + 0.044715f * x * x * x);
+    const float ge = rnd<P>(0.5f * x * (1.f + tanhf(inner)));
+    o[e] = ge * uu;
+  }
+  uint2 pk;
+  pk.x = pack2<P>(o[0], o[1]); pk.y = pack2<P>(o[2], o[3]);
+  *reinterpret_cast<uint2*>(act + (long)t * I + i) = pk;
+}
+
+// final logit soft-cap in fp32 (gemma.py inference: F.linear(...).float(), then / cap, tanh, * cap): one pass, in place
+__global__ __launch_bounds__(256) void softcap_kernel(float* __restrict__ x, long n, float cap) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const long stride = (long)gridDim.x * 256;
+  for (long k = i; k < n; k += stride) x[k] = tanhf(x[k] / cap) * cap;
+}
+
+extern "C" int umb_gemma_rmsnorm(void* out, void* x, const void* w, float eps, float scale, int rows, int H, int dtype,
+                                 hipStream_t st) {
+  if (rows < 1 || H < 4 || H % 4 || H > 16384) return UMB_EINVAL;
+  DISPATCH_DTYPE(dtype, {
+    hipLaunchKernelGGL((gemma_rmsnorm_kernel<P>), dim3(rows), dim3(256), 16 + (size_t)H * 4, st, (u16*)out, (u16*)x,
+                       (const u16*)w, eps, scale, H);
+  })
+  UMB_LAUNCH_CHECK();
+  return UMB_OK;
+}
+
+extern "C" int umb_gemma_sandwich(const float* partial, int S, int T, int H, void* h, void* xn_out, const void* w_post,
+                                  const void* w_next, float eps, int dtype, hipStream_t st) {
+  if (S < 1 || T < 1 || H < 4 || H % 4 || H > 16384 || !w_post || (xn_out && !w_next)) return UMB_EINVAL;
+  DISPATCH_DTYPE(dtype, {
+    hipLaunchKernelGGL((gemma_sandwich_kernel<P>), dim3(T), dim3(256), 16 + (size_t)H * 4, st, partial, S, T, H, (u16*)h,
+                       (u16*)xn_out, (const u16*)w_post, (const u16*)w_next, eps);
+  })
+  UMB_LAUNCH_CHECK();
+  return UMB_OK;
+}
+
+extern "C" int umb_reduce_gelu_mul(const void* partial, int S, int T, int I, void* act, int dtype, hipStream_t st) {
+  if (I % 4 || S < 1 || T < 1) return UMB_EINVAL;
+  const long n4 = (long)T * I / 4;
+  DISPATCH_DTYPE(dtype, {
+    hipLaunchKernelGGL((reduce_gelu_mul_kernel<P>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
+                       (const float*)partial, S, T, I, (u16*)act);
+  })
+  UMB_LAUNCH_CHECK();
+  return UMB_OK;
+}
+
+extern "C" int umb_logit_softcap(float* logits, int64_t n, float cap, hipStream_t st) {
+  if (!logits || n < 0 || !(cap > 0.f)) return UMB_EINVAL;
+  if (n == 0) return UMB_OK;
+  const long blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(softcap_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, st, logits, (long)n, cap);
+  UMB_LAUNCH_CHECK();
+  return UMB_OK;
+}

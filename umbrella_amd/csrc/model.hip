@@ -570,8 +570,10 @@ static UmbLayer rebase(const UmbLayer& in, const void* base) {
   return o;
 }
 
-extern "C" int umb_model_forward_offload(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s,
-                                         const UmbOffload* off, hipStream_t st) {
+// pro(): embedding / prologue; lay(layer, l, next_norm): one decoder layer on the (possibly rebased) layer; hd(): lm_head
+template <class Pro, class Lay, class Head>
+static int offload_forward(const UmbModel* m, const UmbStep* s, const UmbOffload* off, hipStream_t st, Pro&& pro, Lay&& lay,
+                           Head&& hd) {
   const int lb = s->layer_begin, le = s->layer_end;
   if (lb < 0 || le > m->L || lb >= le) return UMB_EINVAL;
   const int NS = off->n_slabs;
@@ -612,12 +614,7 @@ extern "C" int umb_model_forward_offload(const UmbModel* m, const UmbWorkspace* 
   }
   if (pf) for (int i = 0; i < UMB_MAX_SLABS; ++i) pf[i] = -1;
 
-  const bool ll = use_ll(m, ws, s);
-  const int fm = ll ? 0 : split_fm_tt(m, ws, s, nullptr);
-  const bool df = !ll && use_defer(m, ws, s, nullptr);
-  int sg = 4;
-  CK(ll ? prologue_ll(m, ws, s, m->layers[lb].norm1, st)
-        : df ? prologue_defer(m, ws, s, m->layers[lb].norm1, fm, &sg, st) : prologue(m, ws, s, m->layers[lb].norm1, st, fm));
+  CK(pro());
   for (int l = lb; l < le; ++l) {
     UmbLayer cur = m->layers[l];
     int buf = -1;
@@ -627,8 +624,7 @@ extern "C" int umb_model_forward_offload(const UmbModel* m, const UmbWorkspace* 
       cur = rebase(m->layers[l], off->dev_slab[buf]);
     }
     const void* nn = (l + 1 < le) ? m->layers[l + 1].norm1 : (le == m->L ? m->final_norm : nullptr);
-    CK(ll ? layer_ll(m, ws, s, cur, l, nn, &sg, st)
-          : df ? layer_split_defer(m, ws, s, cur, l, nn, &sg, st, fm, l + 1 < le) : layer(m, ws, s, cur, l, nn, st, fm, l + 1 < le));
+    CK(lay(cur, l, nn));
     if (buf >= 0) {
       ++used;
       if (hipEventRecord((hipEvent_t)off->ev_free[buf], st) != hipSuccess) return UMB_EHIP;
@@ -650,8 +646,101 @@ extern "C" int umb_model_forward_offload(const UmbModel* m, const UmbWorkspace* 
       for (int i = 0; i < nfirst; ++i) CK(issue_copy(first[i], i));
     for (int i = 0; i < NS; ++i) pf[i] = first[i];
   }
-  if (le == m->L) CK(ll ? head_ll(m, ws, s, sg, st) : df ? head_defer(m, ws, s, sg, st) : head(m, ws, s, st));
+  if (le == m->L) CK(hd());
   return UMB_OK;
+}
+
+extern "C" int umb_model_forward_offload(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s,
+                                         const UmbOffload* off, hipStream_t st) {
+  const int lb = s->layer_begin, le = s->layer_end;
+  if (lb < 0 || le > m->L || lb >= le) return UMB_EINVAL;
+  const bool ll = use_ll(m, ws, s);
+  const int fm = ll ? 0 : split_fm_tt(m, ws, s, nullptr);
+  const bool df = !ll && use_defer(m, ws, s, nullptr);
+  int sg = 4;
+  return offload_forward(
+      m, s, off, st,
+      [&]() {
+        return ll ? prologue_ll(m, ws, s, m->layers[lb].norm1, st)
+                  : df ? prologue_defer(m, ws, s, m->layers[lb].norm1, fm, &sg, st) : prologue(m, ws, s, m->layers[lb].norm1, st, fm);
+      },
+      [&](const UmbLayer& cur, int l, const void* nn) {
+        return ll ? layer_ll(m, ws, s, cur, l, nn, &sg, st)
+                  : df ? layer_split_defer(m, ws, s, cur, l, nn, &sg, st, fm, l + 1 < le) : layer(m, ws, s, cur, l, nn, st, fm, l + 1 < le);
+      },
+      [&]() { return ll ? head_ll(m, ws, s, sg, st) : df ? head_defer(m, ws, s, sg, st) : head(m, ws, s, st); });
+}
+
+// ---- Gemma-2 (umbrella/models/gemma.py, gemma_layer.py): schedule 0 with Gemma's arithmetic, row-major activations.
+// prologue: embedding gather, h <- round(h * round(sqrt H)), xn <- gemma_norm(h, input_layernorm)
+static int prologue_gemma2(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbGemma2* g, hipStream_t st) {
+  if (s->T < 1 || s->T > ws->Tmax) return UMB_EINVAL;
+  CK(umb_embed_prep(ws->h, s->skip_embed ? nullptr : m->embed, m->H, s->T, s->tokens, s->positions, s->slots,
+                    s->prefix_len, s->tokens_all, s->n_ptr, s->tree_off, s->depth, ws->pos, ws->slot, ws->prefix,
+                    nullptr, nullptr, nullptr, 0, m->dtype, st));
+  return umb_gemma_rmsnorm(ws->xn, ws->h, m->layers[s->layer_begin].norm1, m->eps, s->skip_embed ? 0.f : g->embed_scale,
+                           s->T, m->H, m->dtype, st);
+}
+
+// one Gemma2DecoderLayer: 9 launches (qkv, q/k/v reduce + RoPE + KV append, attention, o, sandwich, gate/up, gelu * up,
+// down, sandwich).  next_norm: the next layer's input_layernorm or the final norm (NULL: leave h only)
+static int layer_gemma2(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbGemma2* g, const UmbLayer& ly,
+                        int l, const void* next_norm, hipStream_t st) {
+  const int T = s->T, dt = m->dtype;
+  char* kc = (char*)m->k_cache + (size_t)l * m->Hkv * m->Lmax * m->D * 2;
+  char* vt = (char*)m->vt_cache + (size_t)l * m->Hkv * VT_LD(m->Lmax) * m->D * 2;
+  const UmbGemma2Norms& gn = g->norms[l];
+  if (ly.qkv_bias || !gn.pre_ff || !gn.post_ff) return UMB_EINVAL;
+  CK(lin(ly.qkv, ws->xn, m->H, ws->partial, T, dt, st, 0, nullptr));
+  CK(umb_reduce_qkv_rope(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
+                         m->rope_sin, ws->q, kc, vt, /*paired=*/1, nullptr, dt, st));
+  const int win = (g->window > 0 && (l & 1) == g->slide_parity) ? g->window : 0;
+  CK(umb_tree_attn_gemma2(ws->attn, ws->q, kc, vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
+                          s->n_mask_keys, T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_splits, m->attn_scale, g->attn_softcap,
+                          ws->pos, win, ws->attn_counters, dt, st));
+  CK(lin(ly.o, ws->attn, m->Hq * m->D, ws->partial, T, dt, st, 0, nullptr, true));
+  CK(umb_gemma_sandwich(ws->partial, eff_s(ly.o, T, true), T, m->H, ws->h, ws->xn, ly.norm2, gn.pre_ff, m->eps, dt, st));
+  // gate/up: a plain [gate; up] stack (not interleaved), split-K partials, GELU * up in the reduce
+  CK(lin(ly.gu, ws->xn, m->H, ws->partial, T, dt, st, 0, nullptr));
+  CK(umb_reduce_gelu_mul(ws->partial, eff_s(ly.gu, T), T, m->I, ws->act, dt, st));
+  CK(lin(ly.down, ws->act, m->I, ws->partial, T, dt, st, 0, nullptr, true));
+  CK(umb_gemma_sandwich(ws->partial, eff_s(ly.down, T, true), T, m->H, ws->h, next_norm ? ws->xn : nullptr, gn.post_ff,
+                        next_norm, m->eps, dt, st));
+  return UMB_OK;
+}
+
+static int head_gemma2(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbGemma2* g, hipStream_t st) {
+  if (s->head_from >= s->T) return UMB_OK;
+  const int rows = s->T - s->head_from;
+  const char* xn = (const char*)ws->xn + (size_t)s->head_from * m->H * 2;
+  CK(lin(m->lm_head, xn, m->H, ws->logits, rows, m->dtype, st, /*EPI_ROUND*/1, nullptr));
+  if (g->final_softcap > 0.f) CK(umb_logit_softcap(ws->logits, (int64_t)rows * m->lm_head.N, g->final_softcap, st));
+  return UMB_OK;
+}
+
+static inline bool gemma2_ok(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbGemma2* g) {
+  return g && g->norms && ws->fused == 0 && s->layer_begin == 0 && s->layer_end == m->L && !s->skip_embed &&
+         g->window >= 0 && (g->slide_parity == 0 || g->slide_parity == 1);
+}
+
+extern "C" int umb_model_forward_gemma2(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbGemma2* g,
+                                        hipStream_t st) {
+  if (!gemma2_ok(m, ws, s, g)) return UMB_EINVAL;
+  CK(prologue_gemma2(m, ws, s, g, st));
+  for (int l = 0; l < m->L; ++l) {
+    const void* nn = l + 1 < m->L ? m->layers[l + 1].norm1 : m->final_norm;
+    CK(layer_gemma2(m, ws, s, g, m->layers[l], l, nn, st));
+  }
+  return head_gemma2(m, ws, s, g, st);
+}
+
+extern "C" int umb_model_forward_gemma2_offload(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s,
+                                                const UmbGemma2* g, const UmbOffload* off, hipStream_t st) {
+  if (!gemma2_ok(m, ws, s, g)) return UMB_EINVAL;
+  return offload_forward(
+      m, s, off, st, [&]() { return prologue_gemma2(m, ws, s, g, st); },
+      [&](const UmbLayer& cur, int l, const void* nn) { return layer_gemma2(m, ws, s, g, cur, l, nn, st); },
+      [&]() { return head_gemma2(m, ws, s, g, st); });
 }
 
 extern "C" const char* umb_version(void) { return "umbrella_hip 0.1 (gfx950)"; }

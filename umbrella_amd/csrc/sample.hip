@@ -655,6 +655,7 @@ extern "C" int umb_kv_compact(void* k_cache, void* vt_cache, const int* res, con
   const size_t sm = (size_t)max_path * D * 2 * 2;
   const dim3 grid(Hkv, L), block(256);
   if (D == 128) hipLaunchKernelGGL((kv_compact_kernel<128>), grid, block, sm, st, (u16*)k_cache, (u16*)vt_cache, res, path, Hkv, Lmax, max_path);
+  else if (D == 256) hipLaunchKernelGGL((kv_compact_kernel<256>), grid, block, sm, st, (u16*)k_cache, (u16*)vt_cache, res, path, Hkv, Lmax, max_path);   // Gemma-2 2B / 9B
   else if (D == 64) hipLaunchKernelGGL((kv_compact_kernel<64>), grid, block, sm, st, (u16*)k_cache, (u16*)vt_cache, res, path, Hkv, Lmax, max_path);
   else if (D == 32) hipLaunchKernelGGL((kv_compact_kernel<32>), grid, block, sm, st, (u16*)k_cache, (u16*)vt_cache, res, path, Hkv, Lmax, max_path);
   else return UMB_EINVAL;

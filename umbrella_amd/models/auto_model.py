@@ -2,8 +2,8 @@
 
 The reference keeps three hub-id dicts (plain / offload / cudagraph) of near-identical
 classes; here one HIP-backed ``Llama`` runtime takes ``offload`` / ``cuda_graph`` flags and covers the reference's Llama,
-Qwen (q/k/v projection bias, umbrella/models/qwen.py:94-96) and Mistral (free head_dim, mistral.py:28,101) classes.
-Accepted names: the Llama, Qwen2.5 / QwQ and Mistral hub ids the reference registers (dims tabulated in
+Qwen (q/k/v projection bias, umbrella/models/qwen.py:94-96) and Mistral (free head_dim, mistral.py:28,101) classes; ``Gemma2`` (models/gemma.py) is the reference's Gemma2 class.
+Accepted names: the Llama, Qwen2.5 / QwQ, Mistral and Gemma-2 hub ids the reference registers (dims tabulated in
 models/config.py -- weights are read from a local HF directory when given one, else
 seeded synthetic tensors of the exact shapes), or a local directory with config.json.
 """
@@ -11,12 +11,20 @@ from __future__ import annotations
 
 import os
 
+import json
+
 from .config import KNOWN
+from .gemma import Gemma2
 from .llama import Llama
 
 
+def _dir_class(path):
+    with open(os.path.join(path, "config.json")) as f:
+        return Gemma2 if json.load(f).get("model_type") == "gemma2" else Llama
+
+
 class AutoModelLM:
-    _MODEL_MAPPING = {name: Llama for name in KNOWN}
+    _MODEL_MAPPING = {name: (Gemma2 if cfg.family == "gemma2" else Llama) for name, cfg in KNOWN.items()}
     _OFFLOAD_MODEL_MAPPING = dict(_MODEL_MAPPING)
     _CUDAGRAPH_MODEL_MAPPING = dict(_MODEL_MAPPING)
 
@@ -31,7 +39,7 @@ class AutoModelLM:
         if model_name in table:
             klass = table[model_name]
         elif os.path.isdir(str(model_name)) and os.path.exists(os.path.join(model_name, "config.json")):
-            klass = Llama
+            klass = _dir_class(model_name)
         else:
             raise ValueError(f"Model type '{model_name}' is not supported{what}. "
                              f"Supported{what} types: {list(table.keys())}")

@@ -42,6 +42,14 @@ class LlamaCfg:
     attention_bias: bool = False      # q/k/v projection bias (Qwen2: umbrella/models/qwen.py:94-96)
     embed_rows: int = 0               # rows of the embedding table when they differ from vocab_size (tensor-parallel shard:
                                       # the table stays whole while the lm_head holds vocab_size = V / P rows); 0 = vocab_size
+    # Gemma-2 (umbrella/models/gemma.py); the defaults are "off" and leave every other family as it was
+    family: str = "llama"             # "gemma2": models/gemma.py Gemma2 runtime
+    attn_logit_softcapping: float = 0.0    # scores -> cap * tanh(scores / cap); 0 = off
+    final_logit_softcapping: float = 0.0   # logits -> cap * tanh(logits / cap); 0 = off
+    query_pre_attn_scalar: float = 0.0     # attention scale query_pre_attn_scalar ** -0.5; 0 = head_dim
+    sliding_window: int = 0           # keys a sliding layer sees (p - c < window); 0 = every layer global
+    sliding_parity: int = 0           # layer l slides when l % 2 == sliding_parity (Gemma-2: the even layers)
+    hidden_activation: str = "silu"   # MLP gate: "silu" or "gelu_pytorch_tanh"
 
     @property
     def q_dim(self):
@@ -50,6 +58,13 @@ class LlamaCfg:
     @property
     def kv_dim(self):
         return self.num_key_value_heads * self.head_dim
+
+    @property
+    def attn_scale(self) -> float:
+        return (self.query_pre_attn_scalar or self.head_dim) ** -0.5
+
+    def is_sliding(self, layer: int) -> bool:
+        return self.sliding_window > 0 and layer % 2 == self.sliding_parity
 
     @classmethod
     def from_dir(cls, path: str) -> "LlamaCfg":
@@ -63,6 +78,8 @@ class LlamaCfg:
             with open(gen) as f:
                 eos = json.load(f).get("eos_token_id", eos)
         q = c.get("quantization_config") or {}
+        if c.get("model_type") == "gemma2":
+            return cls._gemma2_from_dict(c, eos, q, path)
         qwen = c.get("model_type") == "qwen2"
         if qwen:                                    # the reference pins Qwen2.5's vocabulary (qwen.py:12,27)
             c["vocab_size"] = min(c["vocab_size"], 151936)
@@ -78,6 +95,41 @@ class LlamaCfg:
                    eos_token_id=eos if isinstance(eos, list) else [eos],
                    awq=q.get("quant_method") == "awq", awq_group=q.get("group_size", 128),
                    name=os.path.basename(os.path.normpath(path)))
+
+    @classmethod
+    def _gemma2_from_dict(cls, c: dict, eos, q: dict, path: str) -> "LlamaCfg":
+        """HF Gemma2Config (config.json of model_type "gemma2"): layer_types, when present, must alternate sliding / full."""
+        rp = c.get("rope_parameters") or {}
+        lt = c.get("layer_types")
+        parity = 0
+        if lt:
+            slide = [t == "sliding_attention" for t in lt]
+            parity = 0 if slide[0] else 1
+            if any(s != ((i % 2) == parity) for i, s in enumerate(slide)):
+                raise NotImplementedError(f"Gemma-2 layer_types must alternate sliding / full attention, got {lt}")
+        H, Hq = c["hidden_size"], c["num_attention_heads"]
+        D = c.get("head_dim") or H // Hq
+        return cls(family="gemma2", vocab_size=c["vocab_size"], hidden_size=H, intermediate_size=c["intermediate_size"],
+                   num_hidden_layers=c["num_hidden_layers"], num_attention_heads=Hq,
+                   num_key_value_heads=c.get("num_key_value_heads", Hq), head_dim=D,
+                   rms_norm_eps=c.get("rms_norm_eps", 1e-6), rope_theta=c.get("rope_theta") or rp.get("rope_theta", 10000.0),
+                   rope_scaling=None, max_position_embeddings=c.get("max_position_embeddings", 8192),
+                   tie_word_embeddings=c.get("tie_word_embeddings", True),
+                   eos_token_id=eos if isinstance(eos, list) else [eos], awq=q.get("quant_method") == "awq",
+                   # missing keys take HF Gemma2Config's defaults; an explicit null turns the feature off
+                   attn_logit_softcapping=float(c.get("attn_logit_softcapping", 50.0) or 0.0),
+                   final_logit_softcapping=float(c.get("final_logit_softcapping", 30.0) or 0.0),
+                   query_pre_attn_scalar=float(c.get("query_pre_attn_scalar", 256) or D),
+                   sliding_window=int(c.get("sliding_window", 4096) or 0), sliding_parity=parity,
+                   hidden_activation=c.get("hidden_activation") or c.get("hidden_act") or "gelu_pytorch_tanh",
+                   name=os.path.basename(os.path.normpath(path)))
+
+
+def require_family(cfg: LlamaCfg, family: str, what: str) -> None:
+    """Runtimes are per family: a Gemma-2 config on the Llama kernels would run SiLU, Llama norms and 1/sqrt(D) silently."""
+    if cfg.family != family:
+        raise NotImplementedError(f"{what} runs {family} models only; '{cfg.name}' is a {cfg.family} model"
+                                  + (" (models/gemma.py Gemma2: single GPU, resident or offloaded)" if cfg.family == "gemma2" else ""))
 
 
 def _l(**kw):
@@ -162,6 +214,22 @@ KNOWN["Felladrin/Llama-68M-Chat-v1"] = _l(vocab_size=32000, hidden_size=768, int
 # directory with config.json for those.
 KNOWN["meta-llama/Llama-3.2-1B"] = KNOWN["meta-llama/Llama-3.2-1B-Instruct"]
 KNOWN["meta-llama/Meta-Llama-3.1-8B-Instruct"] = KNOWN["meta-llama/Llama-3.1-8B-Instruct"]
+
+
+
+def _gemma2(H, I, L, Hq, Hkv, D, qpas, name):
+    return LlamaCfg(family="gemma2", vocab_size=256000, hidden_size=H, intermediate_size=I, num_hidden_layers=L,
+                    num_attention_heads=Hq, num_key_value_heads=Hkv, head_dim=D, rms_norm_eps=1e-6, rope_theta=10000.0,
+                    rope_scaling=None, max_position_embeddings=8192, tie_word_embeddings=True, eos_token_id=[1, 107],
+                    attn_logit_softcapping=50.0, final_logit_softcapping=30.0, query_pre_attn_scalar=float(qpas),
+                    sliding_window=4096, sliding_parity=0, hidden_activation="gelu_pytorch_tanh", name=name)
+
+
+# Gemma-2 ids the reference maps to its Gemma2 class (auto_model.py:111-114): public HF dims
+KNOWN["google/gemma-2-2b"] = _gemma2(2304, 9216, 26, 8, 4, 256, 256, "gemma-2-2b")
+KNOWN["google/gemma-2-2b-it"] = _gemma2(2304, 9216, 26, 8, 4, 256, 256, "gemma-2-2b-it")
+KNOWN["google/gemma-2-9b-it"] = _gemma2(3584, 14336, 42, 16, 8, 256, 256, "gemma-2-9b-it")
+KNOWN["google/gemma-2-27b-it"] = _gemma2(4608, 36864, 46, 32, 16, 128, 144, "gemma-2-27b-it")
 
 
 def rope_inv_freq(cfg: LlamaCfg) -> tuple[torch.Tensor, float]:

@@ -25,7 +25,7 @@ from .. import _lib
 from .._lib import UmbLayer, UmbLinear, UmbModel, UmbOffload, UmbStep, UmbWorkspace
 from ..attn.cache import TreeKVCache
 from .base import LLMBase
-from .config import KNOWN, LlamaCfg, rope_tables
+from .config import KNOWN, LlamaCfg, require_family, rope_tables
 from .synthetic import LINEARS, linear_shapes, synth_awq_tensors, synth_tensor
 from ..logging_config import setup_logger
 
@@ -177,6 +177,8 @@ def pack_mask_bits(mask: torch.Tensor) -> torch.Tensor:
 
 
 class Llama(LLMBase):
+    FAMILY = "llama"      # config.family this runtime computes (Gemma2: "gemma2")
+    INTERLEAVE_GU = True  # gate/up rows stored as (gate_m, up_m) pairs: SiLU * up is the GEMM epilogue (Gemma2: a plain stack)
     CHUNK = 64          # rows of the default workspace (tree / generic forwards)
     PREFILL_CHUNK = 1024  # prompt tokens per forward when the workspace allows: the matrix-bound verify GEMM streams the
                           # weights once per chunk (70B-AWQ, 2048-token prompt: 4.2 k tok/s at 128, 6.1 k at 256, 6.7 k at
@@ -215,6 +217,7 @@ class Llama(LLMBase):
         else:
             raise ValueError(f"Model type '{model_name}' is not supported. Supported types: {list(KNOWN.keys())} "
                              "or a local directory with config.json")
+        require_family(self.config, self.FAMILY, type(self).__name__)
         if self.sched == "auto":
             self.sched = "split" if (self.config.awq or self.config.hidden_size >= 4096) else "ll"
         c = self.config
@@ -280,7 +283,7 @@ class Llama(LLMBase):
         shapes = linear_shapes(c)
         N = sum(shapes[n][0] for n in names)
         K = shapes[names[0]][1]
-        il = names[0] == "mlp.gate_proj"          # fused [gate; up]: interleave rows, SiLU*up in the GEMM epilogue
+        il = names[0] == "mlp.gate_proj" and self.INTERLEAVE_GU   # fused [gate; up]: interleave rows, SiLU*up in the GEMM epilogue
         rope = (c.head_dim, c.num_attention_heads + c.num_key_value_heads) if names[0] == "self_attn.q_proj" else None
         wb, mb = PackedLinear.packed_bytes(N, K, c.awq)
         w_view = slab[cursor:cursor + (N * K // 2 if c.awq else N * K * 2)]

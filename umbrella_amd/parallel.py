@@ -355,9 +355,11 @@ def build_pipelined_engine(device: str, dtype=torch.float16, seed: int = 0, **co
     Launch with torch.distributed.run, one process per GPU; the process group must already be initialised."""
     import json as _json
 
-    from .models.config import KNOWN, LlamaCfg
+    from .models.config import KNOWN, LlamaCfg, require_family
     from .models.llama import Llama, pack_mask_bits
     from .speculation.static_speculation_engine import resolve_growmap_path
+    t = config.get("model")
+    require_family(KNOWN[t] if t in KNOWN else LlamaCfg.from_dir(t), "llama", "layer pipelining")
     kind = config.pop("engine", "static")
     assert kind in ("static", "dynamic"), kind
     rank, world = dist.get_rank(), dist.get_world_size()

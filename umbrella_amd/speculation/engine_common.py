@@ -96,6 +96,12 @@ class HipEngine(BaseEngine):
         # tree, not only `safe_buffer` (the reference fails with a slice-shape error at the same point; here the kernels
         # would write past the caches).  guard == safe_buffer whenever the tree fits in it (all static growmaps).
         self._guard = max(self.safe_buffer, tree_size + 1)
+        # sliding-window attention (Gemma-2) hides key slot c from a query at position p once p - c >= window: exact for tree
+        # keys (slot >= position) only while every ancestor lies less than `window` positions back, i.e. window > tree depth
+        for mdl in (self.draft_model, self.target_model):
+            win = getattr(mdl.config, "sliding_window", 0)
+            assert not win or win > max_path - 1, (
+                f"sliding_window {win} of {type(mdl).__name__} must exceed the tree depth {max_path - 1}")
         assert self.max_length > self.safe_buffer + self._guard, (
             f"max_length {self.max_length} cannot hold a {tree_size}-node tree plus safe_buffer {self.safe_buffer}")
         self.tokens = torch.zeros(self.max_length + tree_size + 8, dtype=torch.int32, device=dev)

@@ -334,7 +334,9 @@ class TensorParallelLlama:
     def build(cls, cfg: LlamaCfg, source, comm: TPComm, max_length, device, dtype, name="tp", seed=0, force_hook=False):
         """source: a full state dict (sliced here with shard_state_dict), or any mapping name -> THIS rank's slice
         (LazySyntheticShard; a checkpoint reader wrapped with shard_tensor)."""
+        from .models.config import require_family
         from .models.llama import Llama
+        require_family(cfg, "llama", "tensor parallelism")
         lc = local_config(cfg, comm.world)
         sd = dict(shard_state_dict(source, cfg, comm.rank, comm.world)) if isinstance(source, dict) else source
         m = Llama(f"{name}-tp{comm.rank}of{comm.world}", max_length=max_length, device=device, dtype=dtype, state_dict=sd,
@@ -527,10 +529,12 @@ def build_tp_engine(device: str, dtype=torch.float16, seed: int = 0, source=None
     the target's checkpoint (default: seeded synthetic tensors of the configured shapes, UMBRELLA_SYNTHETIC=1)."""
     from .models.auto_model import AutoModelLM
     from .models.config import KNOWN
+    from .models.config import require_family
     from .speculation.auto_engine import AutoEngine
-    comm = comm or TPComm()
     target = config["model"]
     cfg = KNOWN[target] if target in KNOWN else LlamaCfg.from_dir(target)
+    require_family(cfg, "llama", "tensor parallelism")
+    comm = comm or TPComm()
     max_length = config.get("max_length", 8192)
     if source is None:
         source = LazySyntheticShard(cfg, comm.rank, comm.world, device, dtype, seed=seed)

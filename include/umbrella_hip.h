@@ -533,6 +533,43 @@ int umb_model_forward_gemma2(const UmbModel* m, const UmbWorkspace* ws, const Um
 int umb_model_forward_gemma2_offload(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* step, const UmbGemma2* g,
                                      const UmbOffload* off, umb_stream_t stream);
 
+/* ------------------------------------------------------------------ Qwen3 (HF modeling_qwen3; not in the reference) */
+/* umb_reduce_qkv_rope2 with Qwen3Attention's per-head norms between the projection and RoPE (Qwen3Attention.forward:
+ * query_states = q_norm(q_proj(x).view(.., head_dim)), key_states = k_norm(k_proj(x).view(.., head_dim)), then
+ * apply_rotary_pos_emb; Qwen3RMSNorm.forward: weight * (x.float() * rsqrt(mean(x.float()^2) + eps)).to(dtype)).  Per q / k head:
+ * x = round(sum_s partial (* 1/rms) (+ bias)), r = fp32(1 / sqrt(sum_d x^2 / D + qk_eps)) correctly rounded, the squares added per
+ * lane pair then by the 64-lane butterfly (a fixed, documented order); on q / k heads the token's 1/rms is correctly rounded too
+ * (v heads: the estimate of umb_reduce_qkv_rope2, whose rows they equal); y = round(x * r), z = round(w[d] * y), RoPE on
+ * z as umb_reduce_qkv_rope; v heads as umb_reduce_qkv_rope.  q_norm / k_norm: [D] in the model dtype, HF feature order.
+ * D % 32 == 0, D <= 256.  Rows whose position or slot lies outside [0, Lmax) are dropped. */
+int umb_reduce_qkv_rope_qknorm(const void* partial, int S, int T, int Hq, int Hkv, int D, int Lmax, const int* pos,
+                               const int* slot, const void* cosT, const void* sinT, void* q_out, void* k_cache,
+                               void* vt_cache, int paired, const void* bias, const float* ssq_in, int ssq_groups,
+                               int ssq_stride, float ssq_dim, float eps, const void* q_norm, const void* k_norm,
+                               float qk_eps, int dtype, umb_stream_t stream);
+
+typedef struct UmbQwen3Norms {
+  const void* q_norm;               /* self_attn.q_norm.weight [D] */
+  const void* k_norm;               /* self_attn.k_norm.weight [D] */
+} UmbQwen3Norms;
+
+typedef struct UmbQwen3 {
+  float qk_eps;                     /* rms_norm_eps of the two head norms */
+  int32_t pad_;
+  const UmbQwen3Norms* norms;       /* host array, L entries */
+} UmbQwen3;
+
+/* Qwen3ForCausalLM forward (Qwen3DecoderLayer.forward, Qwen3Attention.forward, Qwen3MLP.forward): umb_model_forward's
+ * schedule 0 -- the 8-launch split-K layer for any T, with the deferred RMSNorm and the FM-ordered activations under the same
+ * rules -- with umb_reduce_qkv_rope_qknorm as the q/k/v reduce.  ws->fused != 0 is UMB_EINVAL: the fused, low-latency, GEMV
+ * and persistent-chain q/k/v epilogues hold four rows of a head per thread and cannot see the head's sum of squares.  Whole
+ * model only (layer_begin == 0, layer_end == L).  No host syncs. */
+int umb_model_forward_qwen3(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* step, const UmbQwen3* q,
+                            umb_stream_t stream);
+/* the same with the linears streamed from pinned host slabs as umb_model_forward_offload (all norm weights stay resident) */
+int umb_model_forward_qwen3_offload(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* step, const UmbQwen3* q,
+                                    const UmbOffload* off, umb_stream_t stream);
+
 /* diagnostic: n dependent no-op launches of `blocks` workgroups (dispatch cadence) */
 int umb_bench_launch(int n, int blocks, int* p, umb_stream_t stream);
 

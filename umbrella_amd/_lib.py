@@ -120,6 +120,14 @@ class UmbGemma2(C.Structure):
                 ("norms", C.POINTER(UmbGemma2Norms))]
 
 
+class UmbQwen3Norms(C.Structure):
+    _fields_ = [("q_norm", C.c_void_p), ("k_norm", C.c_void_p)]
+
+
+class UmbQwen3(C.Structure):
+    _fields_ = [("qk_eps", C.c_float), ("pad_", C.c_int32), ("norms", C.POINTER(UmbQwen3Norms))]
+
+
 class UmbOffload(C.Structure):
     _fields_ = [("host_slabs", C.POINTER(C.c_void_p)), ("slab_bytes", C.c_size_t), ("dev_slab", C.c_void_p * MAX_SLABS),
                 ("copy_stream", C.c_void_p), ("ev_copied", C.c_void_p * MAX_SLABS), ("ev_free", C.c_void_p * MAX_SLABS),
@@ -200,6 +208,11 @@ SIGNATURES = {
     "umb_model_forward_gemma2": [C.POINTER(UmbModel), C.POINTER(UmbWorkspace), C.POINTER(UmbStep), C.POINTER(UmbGemma2), _P],
     "umb_model_forward_gemma2_offload": [C.POINTER(UmbModel), C.POINTER(UmbWorkspace), C.POINTER(UmbStep),
                                          C.POINTER(UmbGemma2), C.POINTER(UmbOffload), _P],
+    "umb_reduce_qkv_rope_qknorm": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _F, _P, _P, _F,
+                                   _I, _P],
+    "umb_model_forward_qwen3": [C.POINTER(UmbModel), C.POINTER(UmbWorkspace), C.POINTER(UmbStep), C.POINTER(UmbQwen3), _P],
+    "umb_model_forward_qwen3_offload": [C.POINTER(UmbModel), C.POINTER(UmbWorkspace), C.POINTER(UmbStep),
+                                        C.POINTER(UmbQwen3), C.POINTER(UmbOffload), _P],
     "umb_bench_launch": [_I, _I, _P, _P],
     "umb_version": [],
 }

@@ -318,6 +318,112 @@ __global__ __launch_bounds__(64) void reduce_qkv_rope_kernel(const float* __rest
   }
 }
 
+// ---- the same reduce with Qwen3's per-head q/k RMSNorm between the projection and RoPE (HF modeling_qwen3,
+// Qwen3Attention.forward: q = q_norm(q_proj(x).view(.., D)), k = k_norm(k_proj(x).view(.., D)), then apply_rotary_pos_emb;
+// Qwen3RMSNorm.forward: w * (x_fp32 * rsqrt(mean x_fp32^2 + eps)).to(dtype)).  One 64-lane block per (token, head); a lane
+// keeps its NP pairs (d, d + D/2), d = lane + 64 i, of the head in registers from the split sum to the stores: the head's sum
+// of squares is lane-local over the pairs, then the 64-lane butterfly (fixed order).  NP = 1 up to D = 128, 2 up to 256; v heads
+// skip the norm and RoPE and come out as reduce_qkv_rope_kernel writes them.
+template <typename P, int NP>
+__global__ __launch_bounds__(64) void reduce_qkv_rope_qknorm_kernel(const float* __restrict__ part, int S, int T, int Hq,
+                                                                    int Hkv, int D, int Lmax, const int* __restrict__ pos,
+                                                                    const int* __restrict__ slot,
+                                                                    const u16* __restrict__ cosT, const u16* __restrict__ sinT,
+                                                                    u16* __restrict__ q_out, u16* __restrict__ kc,
+                                                                    u16* __restrict__ vt, int paired,
+                                                                    const u16* __restrict__ bias,
+                                                                    const float* __restrict__ ssq_in, int ssq_groups,
+                                                                    int ssq_stride, float ssq_dim, float eps,
+                                                                    const u16* __restrict__ q_norm,
+                                                                    const u16* __restrict__ k_norm, float qk_eps) {
+  const int t = blockIdx.x, head = blockIdx.y;             // head in [0, Hq + 2*Hkv)
+  const int N = (Hq + 2 * Hkv) * D;
+  const int half = D / 2;
+  const int p = pos[t], sl = slot[t];
+  if (p < 0 || p >= Lmax || sl < 0 || sl >= Lmax) return;  // a row outside the tables / the cache is dropped, never written
+  const bool rot = head < Hq + Hkv;
+  float inv = 1.f;
+  if (ssq_in) {                                            // deferred block norm: per-token 1/rms on the reduced outputs
+    float s = 0.f;
+    for (int q = threadIdx.x; q < ssq_groups; q += 64) s += ssq_in[(long)t * ssq_stride + q];
+    // v heads: the estimate reduce_qkv_rope_kernel uses (their rows are its rows, bit for bit).  q / k heads: 1 / sqrt correctly
+    // rounded -- one unit of the input is up to two of round(w * round(x * r)), so the head norm's input takes no estimate
+    const float v = wave_sum(s) / ssq_dim + eps;
+    inv = rot ? (float)__ddiv_rn(1.0, __dsqrt_rn((double)v)) : rsqrtf(v);
+  }
+  const float* base = part + (long)t * N + head * D;
+  const long sstride = (long)T * N;
+  const bool pr = paired && rot;
+  float a[NP], b[NP];
+  // 1. q_proj(x): split sum in order 0..S-1, 1/rms, bias, one rounding to the model dtype
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    const int d = threadIdx.x + 64 * i;
+    const bool ok = d < half;
+    const int ca = pr ? 2 * d : d, cb = pr ? 2 * d + 1 : d + half;
+    float x = 0.f, y = 0.f;
+    if (ok) {
+      if (S <= 8) {                                        // all partial loads in flight before the first add
+        float va[8], vb[8];
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+          va[s] = s < S ? base[s * sstride + ca] : 0.f;
+          vb[s] = s < S ? base[s * sstride + cb] : 0.f;
+        }
+        x = va[0]; y = vb[0];
+#pragma unroll
+        for (int s = 1; s < 8; ++s)
+          if (s < S) { x += va[s]; y += vb[s]; }           // fixed order 0..S-1
+      } else {
+        x = base[ca]; y = base[cb];
+        for (int s = 1; s < S; ++s) { x += base[s * sstride + ca]; y += base[s * sstride + cb]; }
+      }
+      // product and sum each rounded to fp32 (no contraction into an FMA): the stated order, whatever the compiler prefers
+      x = __fmul_rn(x, inv); y = __fmul_rn(y, inv);
+      if (bias) { x = __fadd_rn(x, P::to_f(bias[head * D + d])); y = __fadd_rn(y, P::to_f(bias[head * D + d + half])); }
+      x = rnd<P>(x); y = rnd<P>(y);
+    }
+    a[i] = x; b[i] = y;
+  }
+  if (!rot) {
+    u16* vo = vt + (long)(head - Hq - Hkv) * D * VT_LD(Lmax);
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const int d = threadIdx.x + 64 * i;
+      if (d < half) { vo[vt_off(d, sl, D)] = P::from_f(a[i]); vo[vt_off(d + half, sl, D)] = P::from_f(b[i]); }
+    }
+    return;
+  }
+  // 2. the head's RMSNorm: fp32 sum of squares of the rounded values (idle lanes hold zeros), y = round(x * r), z = round(w * y)
+  // One pinned order, so that a host restatement can follow it bit for bit: per pair a^2 + b^2 (the squares of 16-bit values are
+  // exact in fp32), pairs added in order i = 0, 1, then the butterfly over lane distances 32, 16, ... 1; mean and + eps rounded
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) ss = __fadd_rn(ss, __fadd_rn(__fmul_rn(a[i], a[i]), __fmul_rn(b[i], b[i])));
+  // 1 / sqrt in correctly rounded double steps, rounded once to fp32: the same bits on any IEEE host (rsqrtf is a 1-unit estimate)
+  const float r = (float)__ddiv_rn(1.0, __dsqrt_rn((double)__fadd_rn(__fdiv_rn(wave_sum(ss), (float)D), qk_eps)));
+  const u16* w = head < Hq ? q_norm : k_norm;              // HF feature order
+  // 3. rotate-half RoPE in the model dtype (each product and the sum rounded, as reduce_qkv_rope_kernel), q out / K append
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    const int d = threadIdx.x + 64 * i;
+    if (d >= half) continue;
+    const float za = mul_rnd<P>(P::to_f(w[d]), rnd_prod<P>(a[i], r));
+    const float zb = mul_rnd<P>(P::to_f(w[d + half]), rnd_prod<P>(b[i], r));
+    const float c0 = P::to_f(cosT[(long)p * D + d]), c1 = P::to_f(cosT[(long)p * D + d + half]);
+    const float s0 = P::to_f(sinT[(long)p * D + d]), s1 = P::to_f(sinT[(long)p * D + d + half]);
+    const float o0 = rnd<P>(mul_rnd<P>(za, c0) + mul_rnd<P>(-zb, s0));
+    const float o1 = rnd<P>(mul_rnd<P>(zb, c1) + mul_rnd<P>(za, s1));
+    if (head < Hq) {
+      u16* qo = q_out + ((long)t * Hq + head) * D;
+      qo[d] = P::from_f(o0); qo[d + half] = P::from_f(o1);
+    } else {
+      u16* ko = kc + (long)(head - Hq) * Lmax * D;            // fragment order inside the head's slab (common.h)
+      ko[kc_off(sl, d, D)] = P::from_f(o0); ko[kc_off(sl, d + half, D)] = P::from_f(o1);
+    }
+  }
+}
+
 // ---- embedding gather + per-forward index prep.
 // TREE mode  (tokens_all != null): token i = tokens_all[n + off + i], pos = n + depth[off+i], slot = n + off + i
 // EXPLICIT   : tokens/pos/slot given; they are copied into the workspace arrays the later kernels read.
@@ -497,6 +603,30 @@ extern "C" int umb_reduce_qkv_rope(const void* partial, int S, int T, int Hq, in
                                    hipStream_t st) {
   return umb_reduce_qkv_rope2(partial, S, T, Hq, Hkv, D, Lmax, pos, slot, cosT, sinT, q_out, k_cache, vt_cache, paired,
                               bias, nullptr, 0, 0, 0.f, 0.f, dtype, st);
+}
+
+extern "C" int umb_reduce_qkv_rope_qknorm(const void* partial, int S, int T, int Hq, int Hkv, int D, int Lmax,
+                                          const int* pos, const int* slot, const void* cosT, const void* sinT, void* q_out,
+                                          void* k_cache, void* vt_cache, int paired, const void* bias, const float* ssq_in,
+                                          int ssq_groups, int ssq_stride, float ssq_dim, float eps, const void* q_norm,
+                                          const void* k_norm, float qk_eps, int dtype, hipStream_t st) {
+  if (D % 32 || D < 32 || D > 256 || Lmax % 32 || S < 1 || T < 1 || Hq < 1 || Hkv < 1 || !q_norm || !k_norm ||
+      (ssq_in && (ssq_groups < 1 || ssq_stride < ssq_groups || ssq_dim <= 0.f)))
+    return UMB_EINVAL;
+  DISPATCH_DTYPE(dtype, {
+    if (D <= 128)
+      hipLaunchKernelGGL((reduce_qkv_rope_qknorm_kernel<P, 1>), dim3(T, Hq + 2 * Hkv), dim3(64), 0, st, (const float*)partial,
+                         S, T, Hq, Hkv, D, Lmax, pos, slot, (const u16*)cosT, (const u16*)sinT, (u16*)q_out, (u16*)k_cache,
+                         (u16*)vt_cache, paired, (const u16*)bias, ssq_in, ssq_groups, ssq_stride, ssq_dim, eps,
+                         (const u16*)q_norm, (const u16*)k_norm, qk_eps);
+    else
+      hipLaunchKernelGGL((reduce_qkv_rope_qknorm_kernel<P, 2>), dim3(T, Hq + 2 * Hkv), dim3(64), 0, st, (const float*)partial,
+                         S, T, Hq, Hkv, D, Lmax, pos, slot, (const u16*)cosT, (const u16*)sinT, (u16*)q_out, (u16*)k_cache,
+                         (u16*)vt_cache, paired, (const u16*)bias, ssq_in, ssq_groups, ssq_stride, ssq_dim, eps,
+                         (const u16*)q_norm, (const u16*)k_norm, qk_eps);
+  })
+  UMB_LAUNCH_CHECK();
+  return UMB_OK;
 }
 
 extern "C" int umb_embed_prep_fm(void* x, const void* table, int H, int T, const int* tok, const int* pos, const int* slot,

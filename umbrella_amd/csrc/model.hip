@@ -102,8 +102,10 @@ static inline int split_fm_tt(const UmbModel* m, const UmbWorkspace* ws, const U
 // as much as a kernel boundary on the 8-XCD part (profiles/README.md), and it serialises a tail onto every GEMM.
 // fm: token tiles of the FM-ordered activations (split_fm_tt; 0 = row-major); more: another layer of THIS forward follows, i.e.
 // the normed residual this layer leaves is a GEMM operand (FM) and not the lm_head's / the next pipeline stage's input (row-major)
+// qn: Qwen3's per-head q / k norm weights of this layer (qk_eps their epsilon), applied by the q/k/v reduce; NULL: none
 static int layer_split(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbLayer& ly, int l,
-                       const void* next_norm, hipStream_t st, const UmbTP* tp = nullptr, int fm = 0, bool more = false) {
+                       const void* next_norm, hipStream_t st, const UmbTP* tp = nullptr, int fm = 0, bool more = false,
+                       const UmbQwen3Norms* qn = nullptr, float qk_eps = 0.f) {
   const int T = s->T, dt = m->dtype;
   const size_t esz = 2;
   char* kc = (char*)m->k_cache + (size_t)l * m->Hkv * m->Lmax * m->D * esz;
@@ -113,8 +115,13 @@ static int layer_split(const UmbModel* m, const UmbWorkspace* ws, const UmbStep*
   fgu.pad1 = 3;                                             // x and the SiLU output in FM order
   const UmbGemmFused* xf = fm ? &fxm : nullptr;
   CK(lin(ly.qkv, ws->xn, m->H, ws->partial, T, dt, st, 0, xf));
-  CK(umb_reduce_qkv_rope(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
-                         m->rope_sin, ws->q, kc, vt, /*paired=*/1, ly.qkv_bias, dt, st));
+  if (qn)
+    CK(umb_reduce_qkv_rope_qknorm(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
+                                  m->rope_sin, ws->q, kc, vt, /*paired=*/1, ly.qkv_bias, nullptr, 0, 0, 0.f, 0.f, qn->q_norm,
+                                  qn->k_norm, qk_eps, dt, st));
+  else
+    CK(umb_reduce_qkv_rope(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
+                           m->rope_sin, ws->q, kc, vt, /*paired=*/1, ly.qkv_bias, dt, st));
   CK(umb_tree_attn2(ws->attn, ws->q, kc, vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
                     s->n_mask_keys, T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_chunk, ws->attn_splits, m->attn_scale,
                     ws->attn_counters, fm, dt, st));
@@ -166,7 +173,8 @@ static int prologue_defer(const UmbModel* m, const UmbWorkspace* ws, const UmbSt
                            ws->hw, first_norm, ws->ssq, ws->ssq_stride, fm, m->dtype, st);
 }
 static int layer_split_defer(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbLayer& ly, int l,
-                             const void* next_norm, int* groups, hipStream_t st, int fm, bool more) {
+                             const void* next_norm, int* groups, hipStream_t st, int fm, bool more,
+                             const UmbQwen3Norms* qn = nullptr, float qk_eps = 0.f) {
   const int T = s->T, dt = m->dtype;
   const size_t esz = 2;
   char* kc = (char*)m->k_cache + (size_t)l * m->Hkv * m->Lmax * m->D * esz;
@@ -175,9 +183,14 @@ static int layer_split_defer(const UmbModel* m, const UmbWorkspace* ws, const Um
   fxm.pad1 = 1;                                             // x in FM order
   const UmbGemmFused* xf = fm ? &fxm : nullptr;
   CK(lin(ly.qkv, ws->hw, m->H, ws->partial, T, dt, st, 0, xf));
-  CK(umb_reduce_qkv_rope2(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
-                          m->rope_sin, ws->q, kc, vt, /*paired=*/1, ly.qkv_bias, ws->ssq, *groups, ws->ssq_stride, (float)m->H,
-                          m->eps, dt, st));
+  if (qn)
+    CK(umb_reduce_qkv_rope_qknorm(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
+                                  m->rope_sin, ws->q, kc, vt, /*paired=*/1, ly.qkv_bias, ws->ssq, *groups, ws->ssq_stride,
+                                  (float)m->H, m->eps, qn->q_norm, qn->k_norm, qk_eps, dt, st));
+  else
+    CK(umb_reduce_qkv_rope2(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
+                            m->rope_sin, ws->q, kc, vt, /*paired=*/1, ly.qkv_bias, ws->ssq, *groups, ws->ssq_stride, (float)m->H,
+                            m->eps, dt, st));
   CK(umb_tree_attn2(ws->attn, ws->q, kc, vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
                     s->n_mask_keys, T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_chunk, ws->attn_splits, m->attn_scale,
                     ws->attn_counters, fm, dt, st));
@@ -741,6 +754,43 @@ extern "C" int umb_model_forward_gemma2_offload(const UmbModel* m, const UmbWork
       m, s, off, st, [&]() { return prologue_gemma2(m, ws, s, g, st); },
       [&](const UmbLayer& cur, int l, const void* nn) { return layer_gemma2(m, ws, s, g, cur, l, nn, st); },
       [&]() { return head_gemma2(m, ws, s, g, st); });
+}
+
+// ---- Qwen3 (HF modeling_qwen3): umb_model_forward's schedule 0 with the per-head q / k RMSNorm in the q/k/v reduce
+// (umb_reduce_qkv_rope_qknorm); the deferred norm and the FM-ordered activations under the rules of model_forward.
+// off == NULL: resident; else the streaming loop of umb_model_forward_offload.
+static int qwen3_forward(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbQwen3* q, const UmbOffload* off,
+                         hipStream_t st) {
+  if (!q || !q->norms || ws->fused != 0 || s->layer_begin != 0 || s->layer_end != m->L || s->skip_embed || m->D > 256)
+    return UMB_EINVAL;
+  for (int l = 0; l < m->L; ++l)
+    if (!q->norms[l].q_norm || !q->norms[l].k_norm) return UMB_EINVAL;
+  const int fm = split_fm_tt(m, ws, s, nullptr);
+  const bool df = use_defer(m, ws, s, nullptr);
+  int sg = 4;
+  auto pro = [&]() {
+    return df ? prologue_defer(m, ws, s, m->layers[0].norm1, fm, &sg, st) : prologue(m, ws, s, m->layers[0].norm1, st, fm);
+  };
+  auto lay = [&](const UmbLayer& cur, int l, const void* nn) {
+    return df ? layer_split_defer(m, ws, s, cur, l, nn, &sg, st, fm, l + 1 < m->L, &q->norms[l], q->qk_eps)
+              : layer_split(m, ws, s, cur, l, nn, st, nullptr, fm, l + 1 < m->L, &q->norms[l], q->qk_eps);
+  };
+  auto hd = [&]() { return df ? head_defer(m, ws, s, sg, st) : head(m, ws, s, st); };
+  if (off) return offload_forward(m, s, off, st, pro, lay, hd);
+  CK(pro());
+  for (int l = 0; l < m->L; ++l) CK(lay(m->layers[l], l, l + 1 < m->L ? m->layers[l + 1].norm1 : m->final_norm));
+  return hd();
+}
+
+extern "C" int umb_model_forward_qwen3(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbQwen3* q,
+                                       hipStream_t st) {
+  return qwen3_forward(m, ws, s, q, nullptr, st);
+}
+
+extern "C" int umb_model_forward_qwen3_offload(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbQwen3* q,
+                                               const UmbOffload* off, hipStream_t st) {
+  if (!off) return UMB_EINVAL;
+  return qwen3_forward(m, ws, s, q, off, st);
 }
 
 extern "C" const char* umb_version(void) { return "umbrella_hip 0.1 (gfx950)"; }

@@ -2,8 +2,9 @@
 
 The reference keeps three hub-id dicts (plain / offload / cudagraph) of near-identical
 classes; here one HIP-backed ``Llama`` runtime takes ``offload`` / ``cuda_graph`` flags and covers the reference's Llama,
-Qwen (q/k/v projection bias, umbrella/models/qwen.py:94-96) and Mistral (free head_dim, mistral.py:28,101) classes; ``Gemma2`` (models/gemma.py) is the reference's Gemma2 class.
-Accepted names: the Llama, Qwen2.5 / QwQ, Mistral and Gemma-2 hub ids the reference registers (dims tabulated in
+Qwen (q/k/v projection bias, umbrella/models/qwen.py:94-96) and Mistral (free head_dim, mistral.py:28,101) classes; ``Gemma2`` (models/gemma.py) is the reference's Gemma2 class; ``Qwen3`` (models/qwen3.py: per-head q/k RMSNorm, HF
+Qwen3ForCausalLM) is a family the reference does not have.
+Accepted names: the Llama, Qwen2.5 / QwQ, Mistral and Gemma-2 hub ids the reference registers and the Qwen3 dense ids (dims tabulated in
 models/config.py -- weights are read from a local HF directory when given one, else
 seeded synthetic tensors of the exact shapes), or a local directory with config.json.
 """
@@ -16,15 +17,18 @@ import json
 from .config import KNOWN
 from .gemma import Gemma2
 from .llama import Llama
+from .qwen3 import Qwen3
+
+_FAMILY_CLASS = {"llama": Llama, "gemma2": Gemma2, "qwen3": Qwen3}
 
 
 def _dir_class(path):
     with open(os.path.join(path, "config.json")) as f:
-        return Gemma2 if json.load(f).get("model_type") == "gemma2" else Llama
+        return {"gemma2": Gemma2, "qwen3": Qwen3}.get(json.load(f).get("model_type"), Llama)
 
 
 class AutoModelLM:
-    _MODEL_MAPPING = {name: (Gemma2 if cfg.family == "gemma2" else Llama) for name, cfg in KNOWN.items()}
+    _MODEL_MAPPING = {name: _FAMILY_CLASS[cfg.family] for name, cfg in KNOWN.items()}
     _OFFLOAD_MODEL_MAPPING = dict(_MODEL_MAPPING)
     _CUDAGRAPH_MODEL_MAPPING = dict(_MODEL_MAPPING)
 

@@ -43,7 +43,7 @@ class LlamaCfg:
     embed_rows: int = 0               # rows of the embedding table when they differ from vocab_size (tensor-parallel shard:
                                       # the table stays whole while the lm_head holds vocab_size = V / P rows); 0 = vocab_size
     # Gemma-2 (umbrella/models/gemma.py); the defaults are "off" and leave every other family as it was
-    family: str = "llama"             # "gemma2": models/gemma.py Gemma2 runtime
+    family: str = "llama"             # "gemma2": models/gemma.py Gemma2 runtime; "qwen3": models/qwen3.py Qwen3 runtime
     attn_logit_softcapping: float = 0.0    # scores -> cap * tanh(scores / cap); 0 = off
     final_logit_softcapping: float = 0.0   # logits -> cap * tanh(logits / cap); 0 = off
     query_pre_attn_scalar: float = 0.0     # attention scale query_pre_attn_scalar ** -0.5; 0 = head_dim
@@ -80,10 +80,19 @@ class LlamaCfg:
         q = c.get("quantization_config") or {}
         if c.get("model_type") == "gemma2":
             return cls._gemma2_from_dict(c, eos, q, path)
+        if c.get("model_type") == "qwen3_moe":
+            raise NotImplementedError("Qwen3-MoE (model_type 'qwen3_moe') is not supported: dense Qwen3 only")
+        family = "llama"
+        if c.get("model_type") == "qwen3":         # HF Qwen3Config: per-head q/k RMSNorm (models/qwen3.py)
+            family = "qwen3"
+            if c.get("use_sliding_window") or any(t != "full_attention" for t in (c.get("layer_types") or [])):
+                raise NotImplementedError("Qwen3 with sliding-window attention layers is not supported "
+                                          f"(use_sliding_window={c.get('use_sliding_window')}, layer_types={c.get('layer_types')})")
         qwen = c.get("model_type") == "qwen2"
         if qwen:                                    # the reference pins Qwen2.5's vocabulary (qwen.py:12,27)
             c["vocab_size"] = min(c["vocab_size"], 151936)
-        return cls(attention_bias=bool(c.get("attention_bias", qwen)), vocab_size=c["vocab_size"], hidden_size=c["hidden_size"],
+        return cls(family=family, attention_bias=bool(c.get("attention_bias", qwen)), vocab_size=c["vocab_size"],
+                   hidden_size=c["hidden_size"],
                    intermediate_size=c["intermediate_size"], num_hidden_layers=c["num_hidden_layers"],
                    num_attention_heads=c["num_attention_heads"],
                    num_key_value_heads=c.get("num_key_value_heads", c["num_attention_heads"]),
@@ -129,7 +138,8 @@ def require_family(cfg: LlamaCfg, family: str, what: str) -> None:
     """Runtimes are per family: a Gemma-2 config on the Llama kernels would run SiLU, Llama norms and 1/sqrt(D) silently."""
     if cfg.family != family:
         raise NotImplementedError(f"{what} runs {family} models only; '{cfg.name}' is a {cfg.family} model"
-                                  + (" (models/gemma.py Gemma2: single GPU, resident or offloaded)" if cfg.family == "gemma2" else ""))
+                                  + (" (models/gemma.py Gemma2: single GPU, resident or offloaded)" if cfg.family == "gemma2" else "")
+                                  + (" (models/qwen3.py Qwen3: single GPU, resident or offloaded)" if cfg.family == "qwen3" else ""))
 
 
 def _l(**kw):
@@ -230,6 +240,24 @@ KNOWN["google/gemma-2-2b"] = _gemma2(2304, 9216, 26, 8, 4, 256, 256, "gemma-2-2b
 KNOWN["google/gemma-2-2b-it"] = _gemma2(2304, 9216, 26, 8, 4, 256, 256, "gemma-2-2b-it")
 KNOWN["google/gemma-2-9b-it"] = _gemma2(3584, 14336, 42, 16, 8, 256, 256, "gemma-2-9b-it")
 KNOWN["google/gemma-2-27b-it"] = _gemma2(4608, 36864, 46, 32, 16, 128, 144, "gemma-2-27b-it")
+
+
+def _qwen3(H, I, L, Hq, Hkv, tie, awq=False, name="qwen3"):
+    return LlamaCfg(family="qwen3", vocab_size=151936, hidden_size=H, intermediate_size=I, num_hidden_layers=L,
+                    num_attention_heads=Hq, num_key_value_heads=Hkv, head_dim=128, rms_norm_eps=1e-6, rope_theta=1000000.0,
+                    rope_scaling=None, max_position_embeddings=40960, tie_word_embeddings=tie,
+                    eos_token_id=[151645, 151643], awq=awq, attention_bias=False, name=name)
+
+
+# Qwen3 dense checkpoints (not in the reference's registry; HF Qwen3ForCausalLM defines them): public dims, head_dim 128 free
+# of hidden_size.  A local directory's config.json always overrides these.
+_QWEN3_DIMS = {"0.6B": (1024, 3072, 28, 16, 8, True), "1.7B": (2048, 6144, 28, 16, 8, True),
+               "4B": (2560, 9728, 36, 32, 8, True), "8B": (4096, 12288, 36, 32, 8, False),
+               "14B": (5120, 17408, 40, 40, 8, False), "32B": (5120, 25600, 64, 64, 8, False)}
+for _size, _d in _QWEN3_DIMS.items():
+    KNOWN[f"Qwen/Qwen3-{_size}"] = _qwen3(*_d, name=f"qwen3-{_size.lower()}")
+    if _size in ("4B", "8B", "14B", "32B"):
+        KNOWN[f"Qwen/Qwen3-{_size}-AWQ"] = _qwen3(*_d, awq=True, name=f"qwen3-{_size.lower()}-awq")
 
 
 def rope_inv_freq(cfg: LlamaCfg) -> tuple[torch.Tensor, float]:

@@ -25,6 +25,9 @@ SysPrompts = {
     "mistral": "",
 }
 
+# Qwen3 speaks the same ChatML as Qwen2.5 (no thinking-mode handling)
+Prompts["qwen3"], SysPrompts["qwen3"] = Prompts["qwen"], SysPrompts["qwen"]
+
 ExtraPrompts = {
     "llama3-code": "\nPrefer complete functions over fragments.",
 }

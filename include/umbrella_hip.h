@@ -262,6 +262,8 @@ int umb_embed_prep_fm(void* x, const void* table, int H, int T, const int* tok, 
 /* flashinfer.single_prefill_with_kv_cache(custom_mask=...) (umbrella/attn/cache.py:77-85) and
  * StaticKV_Cache.compute_attention (cache.py:169-192).  Keys [0,*prefix_len) are visible to every
  * row; key *prefix_len + b is visible to row t iff bit b of mask_bits[t*mask_words ...] (NULL: b <= t).
+ * b < n_mask_keys; with mask_bits != NULL every mask key needs its bit, n_mask_keys <= 64 * mask_words, else -22
+ * (all three entry points).  mask_words may be larger than needed (rows of a wider tree); bits >= n_mask_keys are ignored.
  * po: [max_splits][T][Hq][D] fp32, pml: [max_splits][T][Hq][2] fp32 scratch; chunk*max_splits >= Lmax.
  * One launch: 8 waves per (kv head, 16-row query tile) split the keys and merge in LDS; contexts beyond 2048 keys
  * use further 2048-key span blocks merged by the last arriver, which needs `counters` (>= Hkv * ceil(T*(Hq/Hkv)/16)

@@ -594,6 +594,8 @@ extern "C" int umb_tree_attn2(void* out, const void* q, const void* k_cache, con
                               int Hq, int Hkv, int D, int Lmax, int chunk, int max_splits, float scale,
                               unsigned* counters, int out_fm_tt, int dtype, hipStream_t st) {
   if (T < 1 || Hq % Hkv || chunk % 32 || Lmax % 32 || (D != 32 && D != 64 && D != 128)) return UMB_EINVAL;
+  // every mask key needs its bit: the kernels clamp the word index to mask_words - 1 and rely on key < kv_end for the rest
+  if (mask_bits && (n_mask_keys < 0 || (long)n_mask_keys > 64L * mask_words)) return UMB_EINVAL;
   if (out_fm_tt && (out_fm_tt * 16 < T || (Hq * D) % 32)) return UMB_EINVAL;
   const int nrows = T * (Hq / Hkv);
   const int nqt = (nrows + 15) / 16;
@@ -677,7 +679,7 @@ extern "C" int umb_tree_attn_gemma2(void* out, const void* q, const void* k_cach
                                     int Hq, int Hkv, int D, int Lmax, int max_splits, float scale, float softcap,
                                     const int* pos, int window, unsigned* counters, int dtype, hipStream_t st) {
   if (T < 1 || Hkv < 1 || Hq % Hkv || Lmax % 32 || (D != 128 && D != 256) || !counters || window < 0 || softcap < 0.f ||
-      (window > 0 && !pos))
+      (window > 0 && !pos) || (mask_bits && (n_mask_keys < 0 || (long)n_mask_keys > 64L * mask_words)))
     return UMB_EINVAL;
   const int nqt = (T * (Hq / Hkv) + 15) / 16;
   int KBK, single_max;

@@ -282,7 +282,8 @@ int umb_tree_attn2(void* out, const void* q, const void* k_cache, const void* vt
                    int dtype, umb_stream_t stream);
 
 /* ------------------------------------------------------------------ tree bookkeeping */
-/* target_logits.argmax(-1) (static_speculation_engine.py:307) */
+/* target_logits.argmax(-1) (static_speculation_engine.py:307).  Ties here and in the top-k below: the lower vocabulary
+ * index wins (torch.argmax semantics); -0.0 and +0.0 tie, and a zero comes back from the top-k as +0.0. */
 int umb_argmax_rows(int* out, const float* logits, int rows, int V, umb_stream_t stream);
 /* topk per row (speculation_utils.py:57-61; dynamic_speculation_engine.py:236); optional Sequoia child
  * placement tokens_all[*n_ptr + child_start[row] + r] = idx[r], r < child_cnt[row] (static:115-123,279-281) */
@@ -290,7 +291,7 @@ int umb_topk_rows(int* out_idx, float* out_val, const float* logits, int rows, i
                   const int* n_ptr, const int* child_start, const int* child_cnt, umb_stream_t stream);
 /* the same with each row's vocabulary split over 16 blocks (a single block reads a row at ~50 GB/s); workspace =
  * 4096 bytes of zeroed row counters (self-resetting) + rows * 16 * k * 8 bytes; falls back to umb_topk_rows when the
- * workspace is NULL / too small or V < 16384. */
+ * workspace is NULL / too small, rows > 1024 (the counters), V < 16384 or V % 4 != 0. */
 int umb_topk_rows_ws(int* out_idx, float* out_val, const float* logits, int rows, int V, int k, int* tokens_all,
                      const int* n_ptr, const int* child_start, const int* child_cnt, void* workspace,
                      size_t workspace_bytes, umb_stream_t stream);
@@ -314,15 +315,26 @@ int umb_sample_rows(int* sampled, float* logits, int rows, int V, const int* tok
 int umb_sample_rows_uniform(int* sampled, float* logits, int rows, int V, const int* tokens_all, const int* n_ptr,
                             float penalty, float temperature, int topk, float topp, const float* uniforms, int rounds,
                             int ustride, int dbg_k, int* dbg_idx, float* dbg_p, umb_stream_t stream);
-/* SpecExec beam expansion of one level (dynamic_speculation_engine.py:236-248) */
+/* SpecExec beam expansion of one level (dynamic_speculation_engine.py:236-248): the W best of the w * B candidates, ordered
+ * by (score descending, flat candidate index ascending), become tree nodes [lvl_off + w, lvl_off + w + W); each child's mask
+ * row is its parent's row (all mask_words words) | its own bit.  w <= 64, w * B <= 1024, W <= w * B, else UMB_EINVAL. */
 int umb_beam_expand(const int* top_idx, const float* top_val, int w, int B, int W, int lvl_off, float* tree_score,
                     int* parents, int* tokens_all, const int* n_ptr, void* mask_bits, int mask_words,
                     umb_stream_t stream);
 /* accept scan + token / num_nodes update + EOS search (static:313-341, dynamic:283-316).
- * out5 = {kept, bonus token, eos hit, new num_nodes, raw accept length}; path[i] = i-th accepted tree index */
+ * out5 = {kept, bonus token, eos hit, new num_nodes, raw accept length}; path[i] = i-th accepted tree index, i < kept
+ * (path needs room for the deepest root..leaf chain; entries from `kept` on are not written).
+ * 1 <= T <= 1024, else UMB_EINVAL.  tokens_all[n .. n + a] (a = raw accept length <= T) is rewritten with the accepted
+ * tokens and the bonus token, so tokens_all holds at least *n_ptr + T + 1 entries: a chain of 1024 nodes accepted whole
+ * writes its bonus token at n + 1024. */
 int umb_accept_scan(const int* sampled, const int* parents, int* tokens_all, int* n_ptr, int T, const int* eos,
                     int n_eos, int* out5, int* path, umb_stream_t stream);
-/* KV_Cache.gather_kv_incremental (umbrella/attn/cache.py:41-49) without the tail memset */
+/* KV_Cache.gather_kv_incremental (umbrella/attn/cache.py:41-49) without the tail memset: with keep = res[0] and
+ * n_old = res[3] - res[0] (umb_accept_scan's out5), slot n_old + i <- slot n_old + path[i] for i < keep, every source read
+ * before any destination is written.  PRECONDITION keep <= max_path (max_path = the deepest root..leaf chain of the tree,
+ * which bounds every accept length).  A call that breaks it stays inside `path` and the staging buffer -- the first max_path
+ * nodes move, nothing else is touched -- but the cache then disagrees with *n_ptr, which the scan advanced by keep.
+ * UMB_EINVAL: Lmax % 32 != 0, D not in {32, 64, 128, 256}, max_path < 0, or a staging buffer max_path * D * 4 bytes > 64 KiB. */
 int umb_kv_compact(void* k_cache, void* vt_cache, const int* res, const int* path, int L, int Hkv, int D, int Lmax,
                    int max_path, int dtype, umb_stream_t stream);
 int umb_set_int(int* p, int v, umb_stream_t stream);

@@ -7,18 +7,20 @@
 //   beam expand (topk, local log-softmax, global topk)    dynamic_speculation_engine.py:236-248
 //   accept scan + token/num_nodes update + EOS search     static:313-341 / dynamic:283-316
 //   KV_Cache.gather_kv_incremental                        umbrella/attn/cache.py:41-49
-// Ties: the lower vocabulary index wins (torch.argmax semantics).
+// Ties: the lower vocabulary index wins (torch.argmax semantics); -0.0 and +0.0 tie.
 #include "common.h"
 
-// key that sorts by (value desc, index asc) when compared as unsigned descending
+// key that sorts by (value desc, index asc) when compared as unsigned descending.  Negative values are negated in two's
+// complement (not inverted), so -0.0 and +0.0 share the key 0x80000000: the two zeros tie, as they do for torch.argmax /
+// torch.topk, and the lower index wins.  key_val returns +0.0 for either zero.
 __device__ __forceinline__ unsigned long long mk_key(float v, int idx) {
   unsigned u = __float_as_uint(v);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);          // monotone float -> uint
+  u = (u & 0x80000000u) ? 0u - u : (u | 0x80000000u);      // monotone float -> uint, -0.0 == +0.0
   return ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - idx);
 }
 __device__ __forceinline__ float key_val(unsigned long long k) {
   unsigned u = (unsigned)(k >> 32);
-  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : 0u - u;
   return __uint_as_float(u);
 }
 __device__ __forceinline__ int key_idx(unsigned long long k) { return 0x7fffffff - (int)(k & 0xffffffffu); }
@@ -107,7 +109,9 @@ __device__ __forceinline__ int topk_select(const float* __restrict__ row, int V,
   const unsigned long long thr = thr_s;
   if ((V & 3) == 0) {
     const f32x4* r4 = reinterpret_cast<const f32x4*>(row);
-    const float thr_v = key_val(thr);                       // cheap float pre-filter, exact key compare after
+    // cheap float pre-filter, exact key compare after.  Fewer than k threads hold data when V / 4 < k: the threshold is
+    // then the empty key 0 and every element is a candidate.
+    const float thr_v = thr ? key_val(thr) : -INFINITY;
     for (int i = threadIdx.x; i < (V >> 2); i += 4 * 1024) {
       f32x4 q[4];
 #pragma unroll
@@ -473,14 +477,18 @@ __global__ __launch_bounds__(1024) void accept_scan_kernel(const int* __restrict
   const int a = s_a;
   const int bonus = sampled[spath[a - 1]];
   // tokens[n + i] = spec[path[i]] (i < a) ; tokens[n + a] = bonus.  Read everything first: sources overlap destinations.
-  int mytok = 0, hit = 0;
+  // A chain of T = 1024 nodes accepted whole gives a == 1024: no thread has tid == a, so thread 0 carries the bonus token.
+  int mytok = 0, hit = 0, bonus_hit = 0;
   if (tid < a) mytok = tokens_all[n + spath[tid]];
-  else if (tid == a) mytok = bonus;
-  if (tid <= a)
+  if (tid < a)
     for (int e = 0; e < n_eos; ++e) hit |= (mytok == eos[e]);
+  if (tid == 0)
+    for (int e = 0; e < n_eos; ++e) bonus_hit |= (bonus == eos[e]);
   __syncthreads();
-  if (tid <= a) tokens_all[n + tid] = mytok;
+  if (tid < a) tokens_all[n + tid] = mytok;
+  if (tid == 0) tokens_all[n + a] = bonus;
   if (hit) atomicMin(&first_hit, tid);            // first EOS among accepted + bonus (static:329-341)
+  if (bonus_hit) atomicMin(&first_hit, a);
   __syncthreads();
   const int e = first_hit;
   const int keep = (e != 0x7fffffff) ? e : a;
@@ -493,6 +501,8 @@ __global__ __launch_bounds__(1024) void accept_scan_kernel(const int* __restrict
 
 // ---- KV compaction: slot n_old + path[i] -> n_old + i for i in [1, keep).  One block per
 // (kv head, layer); all sources are staged in LDS before any destination is written.
+// Precondition res[0] <= max_path (the caller sizes max_path to the deepest root..leaf chain).  The min() below only keeps
+// a violating call inside `path` and the staging buffer: the first max_path nodes move, the rest of the path is ignored.
 template <int D>
 __global__ __launch_bounds__(256) void kv_compact_kernel(u16* __restrict__ kc, u16* __restrict__ vt,
                                                          const int* __restrict__ res, const int* __restrict__ path,
@@ -652,7 +662,9 @@ extern "C" int umb_accept_scan(const int* sampled, const int* parents, int* toke
 extern "C" int umb_kv_compact(void* k_cache, void* vt_cache, const int* res, const int* path, int L, int Hkv, int D,
                               int Lmax, int max_path, int dtype_unused, hipStream_t st) {
   if (Lmax % 32) return UMB_EINVAL;                            // fragment-ordered slabs are tiled by 32 keys
+  if (max_path < 0 || L < 1 || Hkv < 1) return UMB_EINVAL;
   const size_t sm = (size_t)max_path * D * 2 * 2;
+  if (sm > 64 * 1024) return UMB_EINVAL;                       // staging buffer beyond what a launch may ask for: refuse, do not skip
   const dim3 grid(Hkv, L), block(256);
   if (D == 128) hipLaunchKernelGGL((kv_compact_kernel<128>), grid, block, sm, st, (u16*)k_cache, (u16*)vt_cache, res, path, Hkv, Lmax, max_path);
   else if (D == 256) hipLaunchKernelGGL((kv_compact_kernel<256>), grid, block, sm, st, (u16*)k_cache, (u16*)vt_cache, res, path, Hkv, Lmax, max_path);   // Gemma-2 2B / 9B

@@ -71,7 +71,11 @@ int umb_gemm_wide_split(int T, int N, int S_plan);
  * (what F.linear(...).float() yields for the lm_head, llama.py:133); 2 fused SiLU(gate)*up
  * (llama.py:107-110): needs S == 1 and interleaved rows, `out` is then 16-bit act[T][N/2].
  * R: low byte = n-tiles per wave; bits 8..15 = the plan's `tb` word: n-tiles per block (0: 4 R), | 0x80 for 8-wave
- * blocks (one block per CU sharing one staged copy of the activations). */
+ * blocks (one block per CU sharing one staged copy of the activations).
+ * S: any value >= 1.  Split s covers the 128-k blocks [s * per, min(K / 128, (s + 1) * per)), per = ceil((K / 128) / S); a
+ * split whose range is empty (K / 128 = 16, S = 5: per = 4, split 4; any S > K / 128) is written as ZEROS by every kernel
+ * family and for every T, so a consumer may always sum all S slabs of out (the reduce kernels and the in-kernel last
+ * arriver of epi 3 / 4 do). */
 int umb_gemm(void* out, const void* x, int ldx, const void* wpacked, const void* meta, int T, int N, int K,
              int awq, int S, int R, int epi, int dtype, umb_stream_t stream);
 

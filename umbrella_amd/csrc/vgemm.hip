@@ -121,7 +121,7 @@ __global__ __launch_bounds__(512) void vgemm_w_kernel(const u32x4* __restrict__ 
   for (int q = 0; q < 2; ++q)
 #pragma unroll
     for (int t = 0; t < TT; ++t) acc[q][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (kb0 >= kb1) return;                          // (never: the host keeps S <= KB)
+  if (kb0 >= kb1) return;                          // (never: umb_vgemm_w_ok refuses a split count that leaves a slab empty)
 
   // ---- sources.  Weights: tile order [N/64][K/128][4] (gemm.hip repack_awq_kernel); this wave's two tiles are adjacent.
   const long wtile0 = ((long)(nb * 4 + (wv8 >> 1)) * KB) * 4 + (wv8 & 1) * 2;
@@ -368,6 +368,9 @@ static inline void vgw_shape(int T, int N, int S, int* nchunk, int* tt) {
 
 extern "C" int umb_vgemm_w_ok(int T, int N, int K, int S, int epi) {
   if (vgw_ver() == 0 || T <= 64 || N % 256 || K % 128 || epi > EPI_SILU || S < 1 || S > K / 128) return 0;
+  // a trailing slab without k-blocks (KB = 16, S = 5: four slabs of 4) must still come back as zeros (umbrella_hip.h: umb_gemm);
+  // the kernel below leaves the block at once and would hand the caller's buffer back unwritten -- gemm.hip's kernels take it
+  { const int KB = K / 128, per = (KB + S - 1) / S; if ((S - 1) * per >= KB) return 0; }
   int nc, tt;
   vgw_shape(T, N, S, &nc, &tt);
   if (tt < 5) return 0;

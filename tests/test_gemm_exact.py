@@ -25,6 +25,11 @@ Why the sums are exact (every bound below is evaluated by test_exactness_bounds 
              activations are sparse (SPARSE_NNZ non-zeros per row), so |out| <= SPARSE_NNZ * XA * WA < 256: an integer
              that bf16 (8 significant bits) and fp16 hold exactly.
 
+  1/rms     the per-token factor rsqrt(sum ssq / dim + eps) of the fused RMSNorm consumers (epi 1, 2) is made a power of two:
+             sums of squares K * 4^m / 8 in 8 groups, dim = K, eps = 0 give 2^-m with m in RMS_M.  acc * 2^-m keeps acc's
+             significand, and |acc| <= SPARSE_NNZ * XA * max(WA, 15) on sparse rows (int4 at scale 1.0), so every expected
+             output is a 16-bit value (test_token_rms_bounds).
+
 One-hot rows (x[t] = e_k) read the repacked weights back with no summation at all, so they may use REAL fp16 scales and pin
 the two dequant contracts: exact form out = fp32(fp16((q - z) * s)); folded form out = fp32(s) * fp32(q - z) (a 15-bit
 product, exact in fp32; the chain -C + (C + q) = q and t = q - z are exact).  SiLU(gate) * up (epi 2) on one-hot rows:
@@ -50,6 +55,9 @@ XA, WA = 3, 3                        # |x|, |dense W| (integers)
 SCALE_EXPS = (-6, -5, -4, -3)        # int4 scales 2^e
 SPARSE_NNZ = 16                      # non-zeros per row where the output is rounded to 16 bits
 GATE_ON = 32.0                       # the non-zero gate value of the SiLU probes
+RMS_M = (-1, 0, 1)                   # per-token exponents m of the sums of squares: 1/rms = 2^-m = 2, 1, 0.5
+RMS_G, RMS_STRIDE = 8, 12            # valid groups per ssq row, row stride (the columns behind the groups are never read)
+T_RMS = (129, 193, 257)              # one wide chunk + a skinny tail; a tail above 64 (all wide); the 144-token items
 T_SKINNY = (1, 15, 16, 17, 31, 32, 33, 48, 63, 64)
 T_WIDE = (65, 128, 129, 192, 193, 256, 257, 300, 385)
 S_SKINNY = (1, 3, 5, 6, 7, 16)       # KB = 16: whole, ragged (6 6 4), empty trailing (4 x 4 + 0), 3 3 3 3 3 1, empty + 1-block, 1-block
@@ -89,6 +97,26 @@ def test_exactness_bounds(K, form):
         v = torch.arange(-256, 257, dtype=torch.float32)
         assert torch.equal(v.to(dt).float(), v)
     assert SPARSE_NNZ * XA * WA <= 256 and GATE_ON * 3 <= 256
+
+
+def test_token_rms_bounds():
+    """test_wide_epilogues_apply_token_rms_exactly: acc * 2^-m has acc's significand, so it is a 16-bit value as soon as
+    |acc| < 2^(significant bits) and the scaled value stays in the normal range."""
+    assert SPARSE_NNZ * XA * WA < 2 ** 8                          # dense: bf16 holds 8 significant bits, fp16 11
+    assert SPARSE_NNZ * XA * 15 < 2 ** 11                         # int4 at scale 1.0, |q - z| <= 15: fp16 only
+    for m in RMS_M:
+        assert SPARSE_NNZ * XA * 15 * 2.0 ** -m < 65504 and 2.0 ** -m >= 2.0 ** -14      # largest / smallest non-zero |acc * inv|
+        for K in (512, K_SMALL):                                  # the groups and their sum are powers of two: exact in fp32
+            v = np.float32(K * 4.0 ** m / RMS_G)
+            assert float(v) * RMS_G == K * 4.0 ** m and float(np.float32(float(v) * RMS_G) / np.float32(K)) == 4.0 ** m
+    # SiLU: gates 32 * {1, 2} stay >= 32 (the identity), gate * up * inv^2 <= 32 * 3 * 4 = 3 * 2^7: two significant bits
+    for f in (1.0, 2.0):
+        assert GATE_ON * f >= 32.0
+        for u in range(-3, 4):
+            for dt in (torch.float16, torch.bfloat16):
+                assert float(torch.tensor(GATE_ON * u * f * f).to(dt)) == GATE_ON * u * f * f
+    # a last-bit error of the hardware rsqrt / divide (2^-23 relative) against half an ulp of the 16-bit formats
+    assert 4 * 2.0 ** -23 < 2.0 ** -12
 
 
 def test_silu_is_the_identity_on_the_gate_set():
@@ -202,7 +230,9 @@ def mk_int4(N, K, dev, seed, il=False, real_scales=False, q=None, z=None, s=None
     if q is None:
         q = torch.randint(0, 16, (K, N), device=dev, generator=g, dtype=torch.uint8)
         z = torch.randint(0, 16, (K // 128, N), device=dev, generator=g, dtype=torch.uint8)
-        if real_scales:
+        if s is not None:
+            pass                                                            # generated codes under the caller's scales
+        elif real_scales:
             s = (torch.rand(K // 128, N, device=dev, generator=g) * 0.02 + 0.002).half()
         else:
             e = torch.randint(0, len(SCALE_EXPS), (K // 128, N), device=dev, generator=g)
@@ -452,6 +482,91 @@ def test_wide_int4_kernels_behind_umb_vgw_0(dev):
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "vgw0"], env=dict(os.environ, UMB_VGW="0"),
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0 and "child ok 7" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
+
+
+# ------------------------------------------------------------------ per-token 1/rms in the wide kernels' direct epilogues
+def rms_fx(T, K, ms, dev):
+    """UmbGemmFused whose ssq_in [T][RMS_STRIDE] makes 1/rms of row t exactly 2^-m_t (m_t cycling through ms): RMS_G valid groups
+    of K * 4^m_t / RMS_G each, 1e9 behind them, ssq_dim = K, eps = 0.  Returns (fx, the buffer it points to, float64 factors)."""
+    from umbrella_amd import _lib
+    m = torch.tensor(ms, dtype=torch.float64, device=dev)[torch.arange(T, device=dev) % len(ms)]
+    ssq = torch.full((T, RMS_STRIDE), 1e9, dtype=torch.float32, device=dev)
+    ssq[:, :RMS_G] = (K * 4.0 ** m / RMS_G).float()[:, None]
+    fx = _lib.UmbGemmFused()
+    fx.ssq_in, fx.ssq_groups, fx.pad0, fx.ssq_dim, fx.eps = ssq.data_ptr(), RMS_G, RMS_STRIDE, float(K), 0.0
+    return fx, ssq, 2.0 ** -m
+
+
+def check_rms_round(o, x64, dtype, S, what, e=None):
+    """epi 1: every slab is float64 product * 1/rms, a value of the model dtype, bit for bit"""
+    T = x64.shape[0]
+    fx, ssq, inv = rms_fx(T, o.K, RMS_M, x64.device)
+    want64 = slab_refs(x64, o.Wd, S).double() * inv[None, :, None]
+    want = want64.to(dtype)
+    assert torch.equal(want.double(), want64), f"{what}: an expected value is not a {dtype} value"
+    with env(**(e or {})):
+        got = run_gemm(o, strided(x64, dtype), T, S, 1, epi=1, fx=fx)
+    print(f"{what}: max |want| {float(want64.abs().max())}, differing values {int((got != want.float()).sum())}")
+    assert_same_bits(got, want.float(), what)
+
+
+def check_rms_silu(kind, dtype, T, dev, what, e=None):
+    """epi 2 on one-hot rows: act[t, m] = gate * up * (1/rms)^2 with 1/rms in {2, 1} (gates 64 or 32: SiLU is the identity)"""
+    I, K = 512, 512
+    o, act64 = cached(("silu", kind, dtype if kind == "dense" else None), lambda: silu_weights(kind, dtype, I, K, dev))
+    ks = probe_ks(K, (1,))
+    ks = [ks[i % len(ks)] for i in range(T)]
+    fx, ssq, inv = rms_fx(T, K, RMS_M[:2], dev)
+    want64 = act64[torch.tensor(ks, device=dev)] * (inv * inv)[:, None]
+    want = want64.to(dtype)
+    assert torch.equal(want.double(), want64), f"{what}: an expected value is not a {dtype} value"
+    act = torch.full((T, I), float("nan"), dtype=dtype, device=dev)
+    with env(**(e or {})):
+        run_gemm(o, strided(onehot(ks, K, dev), dtype), T, 1, 1, epi=2, fx=fx, out=act)
+    print(f"{what}: max |want| {float(want64.abs().max())}, differing values {int((act != want).sum())}")
+    assert_same_bits(act[None], want[None], what)
+
+
+@gpu
+@pytest.mark.parametrize("T", T_RMS)
+@pytest.mark.parametrize("route", ["dense128-f16", "dense128-bf16", "denseR-f16", "denseR-bf16", "int4-128", "vgw"])
+def test_wide_epilogues_apply_token_rms_exactly(dev, route, T):
+    """The per-token 1/rms of the wide kernels' direct epilogues (fx.ssq_in; epi 1 and epi 2), S = 1: verify_gemm_kernel (dense
+    and int4; N = 512 and N = 4096), vgemm_w_kernel, and the skinny kernel on the tail row of T = 129.  The true factors are
+    2, 1, 0.5 and EVERY expected value is exactly representable in the output dtype (asserted here on the float64 expectations;
+    magnitudes: test_token_rms_bounds), so a last-bit difference of the hardware rsqrtf (2^-23 relative) cannot carry a result
+    across a rounding boundary: half a 16-bit ulp is at least 2^-12 relative.  At S = 1 these matrices stay below the 256
+    work items verify_gemm_r_kernel wants, so the denseR routes also run their own split (S = 16), which reaches it; its int4
+    instantiation and verify_gemm_pp_kernel sit behind UMB_VGW=0 (the child-process test below)."""
+    o, dtype, runs = wide_case(dev, route)
+    e = runs[0][1]
+    if o.awq:                                                              # all scales 1.0: acc is an integer
+        o = cached(("wi4s1",), lambda: mk_int4(512, K_SMALL, dev, 26, s=torch.ones(K_SMALL // 128, 512, device=dev).half()))
+    x64 = cached(("xw-sparse", o.K), lambda: int_x(512, o.K, dev, 7 + o.K, nnz=SPARSE_NNZ))[:T]
+    check_rms_round(o, x64, dtype, 1, f"{route} epi 1 T={T} S=1", e)
+    if route.startswith("denseR"):
+        check_rms_round(o, x64, dtype, runs[0][0], f"{route} epi 1 T={T} S={runs[0][0]}", e)
+    check_rms_silu("int4" if o.awq else "dense", dtype, T, dev, f"{route} epi 2 T={T}", e)
+
+
+def _child_vgw0_rms():
+    dev = torch.device("cuda:0")
+    n = 0
+    for N, Ts in ((4096, (257, 385)), (3840, (257, 385))):
+        o = mk_int4(N, K_SMALL, dev, 31 + N, s=torch.ones(K_SMALL // 128, N, device=dev).half())
+        for T in Ts:
+            check_rms_round(o, int_x(T, K_SMALL, dev, T, nnz=SPARSE_NNZ), torch.float16, 16, f"UMB_VGW=0 epi 1 N={N} T={T}")
+            n += 1
+    print(f"child ok {n}")
+
+
+@gpu
+def test_wide_int4_epilogues_behind_umb_vgw_0_apply_token_rms(dev):
+    """epi 1 with the exact per-token factors on verify_gemm_pp_kernel (shared staging at N = 4096, the token-chunk pairing at
+    N = 3840, T = 257) and the int4 verify_gemm_r_kernel (N = 3840, T = 385)"""
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "vgw0-rms"], env=dict(os.environ, UMB_VGW="0"),
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0 and "child ok 4" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
 
 
 # ------------------------------------------------------------------ one-hot probes: the weights read back element by element
@@ -760,4 +875,4 @@ def test_which_defects_the_relative_metric_lets_through():
 
 if __name__ == "__main__":
     sys.path.insert(0, ROOT)
-    {"vgw0": _child_vgw0}[sys.argv[1]]()
+    {"vgw0": _child_vgw0, "vgw0-rms": _child_vgw0_rms}[sys.argv[1]]()

@@ -522,7 +522,7 @@ __global__ __launch_bounds__(256) void draft_chain_kernel(const char* w_o, const
         const float iv = inv;
         const float g0 = rnd_prod<P>(acc[0], iv), u0 = rnd_prod<P>(acc[1], iv);
         const float g1 = rnd_prod<P>(acc[2], iv), u1 = rnd_prod<P>(acc[3], iv);
-        const float a0 = rnd<P>(g0 / (1.f + __expf(-g0))) * u0, a1 = rnd<P>(g1 / (1.f + __expf(-g1))) * u1;
+        const float a0 = silu_mul<P>(g0, u0), a1 = silu_mul<P>(g1, u1);
         const int m0 = (a.I / ncu) * cu + 2 * sa;      // first act column of this slot
         __hip_atomic_store(a.g_act + (size_t)tl * (a.I / 2) + m0 / 2,
                            ((unsigned long long)(tag_base | 2u) << 32) | pack2<P>(a0, a1), RLX_AGENT);

@@ -105,6 +105,8 @@ template <typename P> __device__ __forceinline__ float rnd_prod(float x, float y
   asm volatile("" : "+v"(p));
   return rnd<P>(p);
 }
+// SiLU(gate) * up with the activation rounded to the model dtype first, as eager torch does (umbrella/models/llama.py:107-110)
+template <typename P> __device__ __forceinline__ float silu_mul(float g, float u) { return rnd<P>(g / (1.f + __expf(-g))) * u; }
 template <typename P> __device__ __forceinline__ unsigned pack2(float lo, float hi) {
   return (unsigned)P::from_f(lo) | ((unsigned)P::from_f(hi) << 16);
 }

@@ -191,8 +191,7 @@ __global__ __launch_bounds__(256) void reduce_silu_mul_kernel(const float* __res
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const float gg = rnd<P>(g[e]), uu = rnd<P>(u[e]);     // both GEMM outputs live in the model dtype
-    const float sg = rnd<P>(gg / (1.f + __expf(-gg)));    // F.silu in dtype
-    o[e] = sg * uu;
+    o[e] = silu_mul<P>(gg, uu);                           // F.silu in dtype, then * up
   }
   uint2 pk;
   pk.x = pack2<P>(o[0], o[1]); pk.y = pack2<P>(o[2], o[3]);

@@ -22,6 +22,7 @@
 //     reduces them in a fixed order -> results are bit-identical for any T
 //     (batch-invariant), which is what makes greedy spec == greedy AR exact.
 #include "common.h"
+#include "gemm_fused.h"
 #include <cstring>
 #include <cstdio>
 #include <type_traits>
@@ -111,17 +112,7 @@ __global__ void repack_awq_kernel(const unsigned* __restrict__ qweight, const un
 // half-wave load per chunk through a wave-private LDS slot.  No load of the main loop is predicated (see the kernel).
 // AWQ modes: 0 dense 16-bit weights; 1 int4, dequant folded out of the MFMA (any activation dtype; the default for
 // launches of <= 64 rows); 2 int4 with exact fp16 dequant in registers, W = fp16((q - z) * s) -- bit-identical to what
-// awq_ext.dequantize_weights_cuda produces -- via v_pk_add_f16 / v_pk_mul_f16 (fp16 activations; wide launches).
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-
-// (a & mask) | magic in ONE VALU op.  gfx9 VOP3 may read a single SGPR/constant, so hipcc splits the pattern into
-// v_and + v_or when both constants live in SGPRs; keeping `magic` in a VGPR makes v_and_or_b32 encodable.
-__device__ __forceinline__ unsigned and_or(unsigned a, unsigned mask, unsigned magic_v) {
-  unsigned r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(mask), "v"(magic_v));
-  return r;
-}
-
+// awq_ext.dequantize_weights_cuda produces -- via v_pk_add_f16 / v_pk_mul_f16 (fp16 activations; wide launches; gemm_fused.h).
 template <typename P, int AWQ, int R> struct Stage {
   u32x4 a[R][AWQ ? 1 : 4];
   u32x4 m4[AWQ == 1 ? R : 1];     // folded path: 4 x {scale, zero} for output rows g*4 .. g*4+3
@@ -220,31 +211,11 @@ __device__ __forceinline__ void stage_compute(const Stage<P, AWQ, R>& st, const 
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     if (AWQ == 2) {
-      const unsigned mm = st.m1[r];
-      const _Float16 sc = __builtin_bit_cast(_Float16, (u16)(mm & 0xffffu));
-      const _Float16 zf = __builtin_bit_cast(_Float16, (u16)(mm >> 16));
-      const h2 s2 = {sc, sc};
-      const _Float16 nz = -((_Float16)1024.0f + zf);          // exact: |1024 + z| <= 1039
-      const _Float16 nz16 = -((_Float16)64.0f + zf);
-      const h2 nz2 = {nz, nz}, nz16_2 = {nz16, nz16};
-      const h2 sixteenth = {(_Float16)0.0625f, (_Float16)0.0625f};
-      unsigned magic = 0x64006400u;
+      const DeqMeta dm = deq_meta(st.m1[r]);
+      unsigned magic = F16::MAGIC;
       asm volatile("" : "+v"(magic));                       // pin the magic constant in a VGPR
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const unsigned w = st.a[r][0][s];
-        const unsigned w8 = w >> 8;
-        // nibbles at mantissa bits 0..3 give fp16(1024 + q); at bits 4..7 fp16(1024 + 16 q): one shift per
-        // dword instead of three.  (q - z) is exact in fp16 either way, then one rounding in (q - z) * s.
-        const h2 t0 = __builtin_bit_cast(h2, and_or(w, 0x000F000Fu, magic));
-        const h2 t1 = __builtin_bit_cast(h2, and_or(w, 0x00F000F0u, magic));
-        const h2 t2 = __builtin_bit_cast(h2, and_or(w8, 0x000F000Fu, magic));
-        const h2 t3 = __builtin_bit_cast(h2, and_or(w8, 0x00F000F0u, magic));
-        wf[r][s][0] = __builtin_bit_cast(unsigned, (t0 + nz2) * s2);
-        wf[r][s][1] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(t1, sixteenth, nz16_2) * s2);
-        wf[r][s][2] = __builtin_bit_cast(unsigned, (t2 + nz2) * s2);
-        wf[r][s][3] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(t3, sixteenth, nz16_2) * s2);
-      }
+      for (int s = 0; s < 4; ++s) wf[r][s] = deq_frag(st.a[r][0][s], dm, magic);
     } else {
 #pragma unroll
       for (int s = 0; s < 4; ++s) wf[r][s] = st.a[r][s];
@@ -266,8 +237,6 @@ __device__ __forceinline__ void stage_compute(const Stage<P, AWQ, R>& st, const 
       }
   }
 }
-
-#include "gemm_fused.h"
 
 // -DUMB_GEMM_TRACE (scripts/r3/gemm_trace.py builds a second library with it): wave 0 of every block stamps the constant
 // 100 MHz clock at its phase boundaries into fx.counters (16 x u64 per block; unused by the direct epilogues): 0 entry,
@@ -526,7 +495,7 @@ __global__ __launch_bounds__(64 * NWV) void skinny_gemm_kernel(const u32x4* __re
             // model dtype as eager torch does (umbrella/models/llama.py:107-110).  out is 16-bit [Ttot][N/2].
             v *= inv[tt];
             const float g0 = rnd<P>(v[0]), u0 = rnd<P>(v[1]), g1 = rnd<P>(v[2]), u1 = rnd<P>(v[3]);
-            const float a0 = rnd<P>(g0 / (1.f + __expf(-g0))) * u0, a1 = rnd<P>(g1 / (1.f + __expf(-g1))) * u1;
+            const float a0 = silu_mul<P>(g0, u0), a1 = silu_mul<P>(g1, u1);
             u16* act = reinterpret_cast<u16*>(out);
             const int fa = (nt0 + r) * 8 + g * 2;
             const long off = out_fm ? ((((long)(fa >> 5) * TT + (tok >> 4)) * 64 + ((fa >> 3) & 3) * 16 + (tok & 15)) << 3) + (fa & 7)
@@ -749,28 +718,11 @@ __global__ __launch_bounds__(256) void verify_gemm_kernel(const u32x4* __restric
     for (int q = 0; q < 2; ++q) {
       u32x4 f0, f1;
       if (AWQ) {
-        const unsigned mm = ra[q][0][2];
-        const _Float16 sc = __builtin_bit_cast(_Float16, (u16)(mm & 0xffffu));
-        const _Float16 zf = __builtin_bit_cast(_Float16, (u16)(mm >> 16));
-        const h2 s2 = {sc, sc};
-        const _Float16 nz = -((_Float16)1024.0f + zf), nz16 = -((_Float16)64.0f + zf);
-        const h2 nz2 = {nz, nz}, nz16_2 = {nz16, nz16};
-        const h2 sixteenth = {(_Float16)0.0625f, (_Float16)0.0625f};
-        unsigned magic = 0x64006400u;
+        const DeqMeta dm = deq_meta(ra[q][0][2]);
+        unsigned magic = F16::MAGIC;
         asm volatile("" : "+v"(magic));
-#pragma unroll
-        for (int sx = 0; sx < 2; ++sx) {
-          const unsigned w = ra[q][0][sx], w8 = w >> 8;
-          const h2 q0 = __builtin_bit_cast(h2, and_or(w, 0x000F000Fu, magic));
-          const h2 q1 = __builtin_bit_cast(h2, and_or(w, 0x00F000F0u, magic));
-          const h2 q2 = __builtin_bit_cast(h2, and_or(w8, 0x000F000Fu, magic));
-          const h2 q3 = __builtin_bit_cast(h2, and_or(w8, 0x00F000F0u, magic));
-          u32x4& f = sx ? f1 : f0;
-          f[0] = __builtin_bit_cast(unsigned, (q0 + nz2) * s2);
-          f[1] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(q1, sixteenth, nz16_2) * s2);
-          f[2] = __builtin_bit_cast(unsigned, (q2 + nz2) * s2);
-          f[3] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(q3, sixteenth, nz16_2) * s2);
-        }
+        f0 = deq_frag(ra[q][0][0], dm, magic);
+        f1 = deq_frag(ra[q][0][1], dm, magic);
       } else {
         f0 = ra[q][0]; f1 = ra[q][AWQ ? 0 : 1];
       }
@@ -809,28 +761,9 @@ __global__ __launch_bounds__(256) void verify_gemm_kernel(const u32x4* __restric
   for (int t4 = 0; t4 < 4; ++t4) {
     const int tok = t0 + (wt * 4 + t4) * 16 + j;
     if (tok >= Tv) continue;
-    float inv = 1.f;
-    if (fx.ssq_in) {                                                 // per-token 1/rms (fused RMSNorm consumers only)
-      const float* sq = fx.ssq_in + (long)tok * (fx.ssq_stride ? fx.ssq_stride : fx.ssq_groups);
-      float a = 0.f;
-      for (int q = 0; q < fx.ssq_groups; q += 4) { const f32x4 v = *reinterpret_cast<const f32x4*>(sq + q); a += v[0]; a += v[1]; a += v[2]; a += v[3]; }
-      inv = rsqrtf(a / fx.ssq_dim + fx.eps);
-    }
+    const float inv = gemm_token_inv(fx, tok);
 #pragma unroll
-    for (int n4 = 0; n4 < 4; ++n4) {
-      f32x4 v = acc[n4][t4];
-      const int ntile = nb * 8 + wn * 4 + n4;
-      if (epi == EPI_SILU) {
-        v *= inv;
-        const float g0 = rnd<P>(v[0]), u0 = rnd<P>(v[1]), g1 = rnd<P>(v[2]), u1 = rnd<P>(v[3]);
-        const float a0 = rnd<P>(g0 / (1.f + __expf(-g0))) * u0, a1 = rnd<P>(g1 / (1.f + __expf(-g1))) * u1;
-        u16* act = reinterpret_cast<u16*>(out);
-        *reinterpret_cast<unsigned*>(act + (long)tok * (N / 2) + ntile * 8 + g * 2) = pack2<P>(a0, a1);
-      } else {
-        if (epi == EPI_ROUND) { v *= inv; v[0] = rnd<P>(v[0]); v[1] = rnd<P>(v[1]); v[2] = rnd<P>(v[2]); v[3] = rnd<P>(v[3]); }
-        *reinterpret_cast<f32x4*>(out + ((long)sp * T + tok) * N + ntile * 16 + g * 4) = v;
-      }
-    }
+    for (int n4 = 0; n4 < 4; ++n4) gemm_store_direct<P>(acc[n4][t4], inv, epi, out, sp, T, tok, N, nb * 8 + wn * 4 + n4, g);
   }
 }
 
@@ -921,29 +854,18 @@ __global__ __launch_bounds__(256, 2) void verify_gemm_r_kernel(const u32x4* __re
     for (int q = 0; q < 4; ++q) {
       if (!AWQ) { wf[q][0] = rd[AWQ ? 0 : q][0]; wf[q][1] = rd[AWQ ? 0 : q][1]; continue; }
       const unsigned mm = rm[q];
-      const _Float16 sc = __builtin_bit_cast(_Float16, (u16)(mm & 0xffffu));
-      const _Float16 zf = __builtin_bit_cast(_Float16, (u16)(mm >> 16));
-      const h2 s2 = {sc, sc};
-      const _Float16 nz = -((_Float16)1024.0f + zf), nz16 = -((_Float16)64.0f + zf);
-      const h2 nz2 = {nz, nz}, nz16_2 = {nz16, nz16};
-      const h2 sixteenth = {(_Float16)0.0625f, (_Float16)0.0625f};
-      unsigned magic = 0x64006400u;
+      const DeqMeta dm = deq_meta(mm);
+      unsigned magic = F16::MAGIC;
       asm volatile("" : "+v"(magic));
 #pragma unroll
       for (int sx = 0; sx < 2; ++sx) {
-        const unsigned w = sx ? ra[q].y : ra[q].x, w8 = w >> 8;
-        const h2 q0 = __builtin_bit_cast(h2, and_or(w, 0x000F000Fu, magic));
-        const h2 q1 = __builtin_bit_cast(h2, and_or(w, 0x00F000F0u, magic));
-        const h2 q2 = __builtin_bit_cast(h2, and_or(w8, 0x000F000Fu, magic));
-        const h2 q3 = __builtin_bit_cast(h2, and_or(w8, 0x00F000F0u, magic));
+        const unsigned w = sx ? ra[q].y : ra[q].x;
 #ifdef UMB_VG_NODEQ       // ablation (wrong results): raw bits as the operand, no dequant arithmetic
+        const unsigned w8 = w >> 8;
         wf[q][sx][0] = w ^ mm; wf[q][sx][1] = w8; wf[q][sx][2] = w; wf[q][sx][3] = w8 ^ mm;
-        (void)q0; (void)q1; (void)q2; (void)q3; (void)s2; (void)nz2; (void)nz16_2; (void)sixteenth;
+        (void)dm;
 #else
-        wf[q][sx][0] = __builtin_bit_cast(unsigned, (q0 + nz2) * s2);
-        wf[q][sx][1] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(q1, sixteenth, nz16_2) * s2);
-        wf[q][sx][2] = __builtin_bit_cast(unsigned, (q2 + nz2) * s2);
-        wf[q][sx][3] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(q3, sixteenth, nz16_2) * s2);
+        wf[q][sx] = deq_frag(w, dm, magic);
 #endif
       }
     }
@@ -983,28 +905,9 @@ __global__ __launch_bounds__(256, 2) void verify_gemm_r_kernel(const u32x4* __re
   for (int t = 0; t < TT; ++t) {
     const int tok = t0 + t * 16 + j;
     if (tok >= Tv) continue;
-    float inv = 1.f;
-    if (fx.ssq_in) {
-      const float* sq = fx.ssq_in + (long)tok * (fx.ssq_stride ? fx.ssq_stride : fx.ssq_groups);
-      float a = 0.f;
-      for (int q = 0; q < fx.ssq_groups; q += 4) { const f32x4 v = *reinterpret_cast<const f32x4*>(sq + q); a += v[0]; a += v[1]; a += v[2]; a += v[3]; }
-      inv = rsqrtf(a / fx.ssq_dim + fx.eps);
-    }
+    const float inv = gemm_token_inv(fx, tok);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      f32x4 v = acc[q][t];
-      const int ntile = (nb * 4 + wv) * 4 + q;
-      if (epi == EPI_SILU) {
-        v *= inv;
-        const float g0 = rnd<P>(v[0]), u0 = rnd<P>(v[1]), g1 = rnd<P>(v[2]), u1 = rnd<P>(v[3]);
-        const float a0 = rnd<P>(g0 / (1.f + __expf(-g0))) * u0, a1 = rnd<P>(g1 / (1.f + __expf(-g1))) * u1;
-        u16* act = reinterpret_cast<u16*>(out);
-        *reinterpret_cast<unsigned*>(act + (long)tok * (N / 2) + ntile * 8 + g * 2) = pack2<P>(a0, a1);
-      } else {
-        if (epi == EPI_ROUND) { v *= inv; v[0] = rnd<P>(v[0]); v[1] = rnd<P>(v[1]); v[2] = rnd<P>(v[2]); v[3] = rnd<P>(v[3]); }
-        *reinterpret_cast<f32x4*>(out + ((long)sp * T + tok) * N + ntile * 16 + g * 4) = v;
-      }
-    }
+    for (int q = 0; q < 4; ++q) gemm_store_direct<P>(acc[q][t], inv, epi, out, sp, T, tok, N, (nb * 4 + wv) * 4 + q, g);
   }
 }
 
@@ -1153,29 +1056,18 @@ __global__ __launch_bounds__(512) void verify_gemm_pp_kernel(const u32x4* __rest
     for (int q = 0; q < 4; ++q) {
       if (!AWQ) { wf[q][0] = rd[AWQ ? 0 : q][AWQ ? 0 : HF * 2]; wf[q][1] = rd[AWQ ? 0 : q][AWQ ? 0 : HF * 2 + 1]; continue; }
       const unsigned mm = rm[q];
-      const _Float16 sc = __builtin_bit_cast(_Float16, (u16)(mm & 0xffffu));
-      const _Float16 zf = __builtin_bit_cast(_Float16, (u16)(mm >> 16));
-      const h2 s2 = {sc, sc};
-      const _Float16 nz = -((_Float16)1024.0f + zf), nz16 = -((_Float16)64.0f + zf);
-      const h2 nz2 = {nz, nz}, nz16_2 = {nz16, nz16};
-      const h2 sixteenth = {(_Float16)0.0625f, (_Float16)0.0625f};
-      unsigned magic = 0x64006400u;
+      const DeqMeta dm = deq_meta(mm);
+      unsigned magic = F16::MAGIC;
       asm volatile("" : "+v"(magic));
 #pragma unroll
       for (int sx = 0; sx < 2; ++sx) {
-        const unsigned w = ra[q][HF * 2 + sx], w8 = w >> 8;
-        const h2 q0 = __builtin_bit_cast(h2, and_or(w, 0x000F000Fu, magic));
-        const h2 q1 = __builtin_bit_cast(h2, and_or(w, 0x00F000F0u, magic));
-        const h2 q2 = __builtin_bit_cast(h2, and_or(w8, 0x000F000Fu, magic));
-        const h2 q3 = __builtin_bit_cast(h2, and_or(w8, 0x00F000F0u, magic));
+        const unsigned w = ra[q][HF * 2 + sx];
 #ifdef UMB_VG_NODEQ       // ablation (wrong results): raw bits as the operand, no dequant arithmetic
+        const unsigned w8 = w >> 8;
         wf[q][sx][0] = w ^ mm; wf[q][sx][1] = w8; wf[q][sx][2] = w; wf[q][sx][3] = w8 ^ mm;
-        (void)q0; (void)q1; (void)q2; (void)q3; (void)s2; (void)nz2; (void)nz16_2; (void)sixteenth;
+        (void)dm;
 #else
-        wf[q][sx][0] = __builtin_bit_cast(unsigned, (q0 + nz2) * s2);
-        wf[q][sx][1] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(q1, sixteenth, nz16_2) * s2);
-        wf[q][sx][2] = __builtin_bit_cast(unsigned, (q2 + nz2) * s2);
-        wf[q][sx][3] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(q3, sixteenth, nz16_2) * s2);
+        wf[q][sx] = deq_frag(w, dm, magic);
 #endif
       }
     }
@@ -1271,31 +1163,37 @@ __global__ __launch_bounds__(512) void verify_gemm_pp_kernel(const u32x4* __rest
   for (int t = 0; t < TT; ++t) {
     const int tok = t0 + t * 16 + j;
     if (tok >= Tv) continue;
-    float inv = 1.f;
-    if (fx.ssq_in) {
-      const float* sq = fx.ssq_in + (long)tok * (fx.ssq_stride ? fx.ssq_stride : fx.ssq_groups);
-      float a = 0.f;
-      for (int q = 0; q < fx.ssq_groups; q += 4) { const f32x4 v = *reinterpret_cast<const f32x4*>(sq + q); a += v[0]; a += v[1]; a += v[2]; a += v[3]; }
-      inv = rsqrtf(a / fx.ssq_dim + fx.eps);
-    }
+    const float inv = gemm_token_inv(fx, tok);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      f32x4 v = acc[q][t];
-      const int ntile = (nb * 4 + wv) * 4 + q;
-      if (epi == EPI_SILU) {
-        v *= inv;
-        const float g0 = rnd<P>(v[0]), u0 = rnd<P>(v[1]), g1 = rnd<P>(v[2]), u1 = rnd<P>(v[3]);
-        const float a0 = rnd<P>(g0 / (1.f + __expf(-g0))) * u0, a1 = rnd<P>(g1 / (1.f + __expf(-g1))) * u1;
-        u16* act = reinterpret_cast<u16*>(out);
-        *reinterpret_cast<unsigned*>(act + (long)tok * (N / 2) + ntile * 8 + g * 2) = pack2<P>(a0, a1);
-      } else {
-        if (epi == EPI_ROUND) { v *= inv; v[0] = rnd<P>(v[0]); v[1] = rnd<P>(v[1]); v[2] = rnd<P>(v[2]); v[3] = rnd<P>(v[3]); }
-        *reinterpret_cast<f32x4*>(out + ((long)sp * T + tok) * N + ntile * 16 + g * 4) = v;
-      }
-    }
+    for (int q = 0; q < 4; ++q) gemm_store_direct<P>(acc[q][t], inv, epi, out, sp, T, tok, N, (nb * 4 + wv) * 4 + q, g);
   }
 }
 
+// Launchers of the two register-tiled wide kernels: the grid and the LDS size follow from the work-item shape (TT token tiles,
+// SHX) alone.
+template <typename P, int AWQ, int TT, int SHX>
+static int launch_vpp(const void* wp, const void* meta, const u16* x, int ldx, float* out, int T, int Tv, int N, int K,
+                      int S, int epi, int pair_tc, const GemmFused& fx, hipStream_t st) {
+  const int nch = (Tv + TT * 16 - 1) / (TT * 16);
+  constexpr size_t smem = (size_t)(2 * TT * 2 + SHX) * 64 * 16;      // two buffers of TT x 2 fragments (SHX: + the dump slot)
+  hipLaunchKernelGGL((verify_gemm_pp_kernel<P, AWQ, TT, SHX>), dim3((unsigned)((N / 256) * nch * S / 2)), dim3(512), smem, st,
+                     (const u32x4*)wp, (const unsigned char*)meta, x, ldx, T, Tv, N, K, S, epi, SHX ? 0 : pair_tc, out, fx);
+  UMB_LAUNCH_CHECK();
+  return UMB_OK;
+}
+
+template <typename P, int AWQ, int TT>
+static int launch_vr(const void* wp, const void* meta, const u16* x, int ldx, float* out, int T, int Tv, int N, int K,
+                     int S, int epi, const GemmFused& fx, hipStream_t st) {
+  const int nch = (Tv + TT * 16 - 1) / (TT * 16);
+  constexpr size_t smem = (size_t)2 * TT * 2 * 64 * 16;
+  hipLaunchKernelGGL((verify_gemm_r_kernel<P, AWQ, TT>), dim3((unsigned)((N / 256) * nch * S)), dim3(256), smem, st,
+                     (const u32x4*)wp, (const unsigned char*)meta, x, ldx, out, T, Tv, N, K, S, epi, fx);
+  UMB_LAUNCH_CHECK();
+  return UMB_OK;
+}
+
+// tt9: 144-token work items (launch_tt); otherwise 128-token ones
 template <typename P, int AWQ>
 static int launch_verify(const void* wp, const void* meta, const u16* x, int ldx, float* out, int T, int Tv, int N,
                          int K, int S, int epi, const GemmFused& fx, hipStream_t st, bool tt9 = false) {
@@ -1306,47 +1204,21 @@ static int launch_verify(const void* wp, const void* meta, const u16* x, int ldx
     if (!plain && N % 256 == 0 && (N / 256) * nchunk * S >= 256) {
       // two-phase schedule: two work items per 8-wave workgroup (UMB_VG_PP=0: the two-blocks-per-CU kernel, A/B)
       static const bool no_pp = getenv("UMB_VG_PP") != nullptr && atoi(getenv("UMB_VG_PP")) == 0;
-      const int nch = tt9 ? (Tv + 143) / 144 : nchunk;
-      const int pair_tc = nch % 2 == 0;
+      const int pair_tc = (tt9 ? (Tv + 143) / 144 : nchunk) % 2 == 0;
       if constexpr (AWQ == 2) if (!no_pp && (pair_tc || (N / 256) % 2 == 0)) {      // int4 only (a dense 128-k block of tiles is 64 registers)
-        const unsigned grid = (unsigned)((N / 256) * nch * S / 2);
         // shared activation staging: the two work items are neighbouring row blocks of one token chunk (UMB_PP_SHX=0: the
         // round-3 pairing -- same rows, neighbouring token chunks, each group staging its own activations)
         static const bool shx = getenv("UMB_PP_SHX") == nullptr || atoi(getenv("UMB_PP_SHX")) != 0;
-        if (shx && (N / 256) % 2 == 0) {
-          if (tt9) {
-            hipLaunchKernelGGL((verify_gemm_pp_kernel<P, AWQ, 9, 1>), dim3(grid), dim3(512), (size_t)(2 * 18 + 1) * 64 * 16, st,
-                               (const u32x4*)wp, (const unsigned char*)meta, x, ldx, T, Tv, N, K, S, epi, 0, out, fx);
-          } else {
-            hipLaunchKernelGGL((verify_gemm_pp_kernel<P, AWQ, 8, 1>), dim3(grid), dim3(512), (size_t)(2 * 16 + 1) * 64 * 16, st,
-                               (const u32x4*)wp, (const unsigned char*)meta, x, ldx, T, Tv, N, K, S, epi, 0, out, fx);
-          }
-          UMB_LAUNCH_CHECK();
-          return UMB_OK;
-        }
-        if (tt9) {
-          hipLaunchKernelGGL((verify_gemm_pp_kernel<P, AWQ, 9>), dim3(grid), dim3(512), (size_t)2 * 18 * 64 * 16, st,
-                             (const u32x4*)wp, (const unsigned char*)meta, x, ldx, T, Tv, N, K, S, epi, pair_tc, out, fx);
-        } else {
-          hipLaunchKernelGGL((verify_gemm_pp_kernel<P, AWQ, 8>), dim3(grid), dim3(512), (size_t)2 * 16 * 64 * 16, st,
-                             (const u32x4*)wp, (const unsigned char*)meta, x, ldx, T, Tv, N, K, S, epi, pair_tc, out, fx);
-        }
-        UMB_LAUNCH_CHECK();
-        return UMB_OK;
+        if (shx && (N / 256) % 2 == 0)
+          return tt9 ? launch_vpp<P, AWQ, 9, 1>(wp, meta, x, ldx, out, T, Tv, N, K, S, epi, 0, fx, st)
+                     : launch_vpp<P, AWQ, 8, 1>(wp, meta, x, ldx, out, T, Tv, N, K, S, epi, 0, fx, st);
+        return tt9 ? launch_vpp<P, AWQ, 9, 0>(wp, meta, x, ldx, out, T, Tv, N, K, S, epi, pair_tc, fx, st)
+                   : launch_vpp<P, AWQ, 8, 0>(wp, meta, x, ldx, out, T, Tv, N, K, S, epi, pair_tc, fx, st);
       }
-      if (tt9) {
-        hipLaunchKernelGGL((verify_gemm_r_kernel<P, AWQ, 9>), dim3((unsigned)((N / 256) * ((Tv + 143) / 144) * S)),
-                           dim3(256), (size_t)2 * 18 * 64 * 16, st, (const u32x4*)wp, (const unsigned char*)meta, x, ldx,
-                           out, T, Tv, N, K, S, epi, fx);
-      } else {
-        hipLaunchKernelGGL((verify_gemm_r_kernel<P, AWQ, 8>), dim3((unsigned)((N / 256) * nchunk * S)), dim3(256),
-                           (size_t)2 * 16 * 64 * 16, st, (const u32x4*)wp, (const unsigned char*)meta, x, ldx, out, T, Tv,
-                           N, K, S, epi, fx);
-      }
-      UMB_LAUNCH_CHECK();
-      return UMB_OK;
+      return tt9 ? launch_vr<P, AWQ, 9>(wp, meta, x, ldx, out, T, Tv, N, K, S, epi, fx, st)
+                 : launch_vr<P, AWQ, 8>(wp, meta, x, ldx, out, T, Tv, N, K, S, epi, fx, st);
     }
-    if (tt9) return UMB_EINVAL;                                      // caller checks r_kernel_ok() first
+    if (tt9) return UMB_EINVAL;                                      // launch_tt asks for 144-token items under the condition above only
   }
   const size_t smem = (size_t)(2 * 8 * 2 + 2 * 8 * 2) * 64 * 16;     // 64 KiB
   hipLaunchKernelGGL((verify_gemm_kernel<P, AWQ>), dim3((unsigned)((N / 128) * nchunk * S)), dim3(256), smem, st,
@@ -1497,7 +1369,7 @@ static int launch_r(int R, const void* wp, const void* meta, const u16* x, int l
 template <typename P, int AWQ>
 static int launch_tt(const void* wp, const void* meta, const u16* x, int ldx, float* out, int T, int N, int K, int R,
                      int S, int epi, const GemmFused& fx0, hipStream_t st, int tb = 0) {
-  // tokens beyond 64 go through further launches (weights re-read from L2/HBM)
+  // T > 64: the wide kernels where they apply; the rest (and every T <= 64) in skinny launches of 64 tokens
   const long ostride = (epi == EPI_SILU) ? (long)(N / 2) / 2 : (long)N;   // out rows in units of float
   int tdone = 0;
   if constexpr (AWQ != 1) {
@@ -1517,10 +1389,10 @@ static int launch_tt(const void* wp, const void* meta, const u16* x, int ldx, fl
       if (rc || tdone == T) return rc;
     }
   }
-  // token chunking: 64 per launch.  A 256-token variant of this kernel (TT = 16, one n-tile per wave) was measured
-  // SLOWER per token (1600 vs 4 x 314 us per 70B layer): every MFMA pulls its 1 KiB B fragment from LDS, which
-  // pins the matrix pipe to the LDS rate with one wave per SIMD.  The large-T verify needs a register-tiled
-  // (R x TT per wave) kernel -- next round; until then weights are re-read once per 64 tokens.
+  // What is left (a tail of <= 64 tokens, T <= 64, the folded int4 form, the split epilogues, N % 128 != 0) goes through the
+  // skinny kernel, 64 tokens per launch, weights re-read once per launch.  A 256-token variant of that kernel (TT = 16, one
+  // n-tile per wave) was measured SLOWER per token (1600 vs 4 x 314 us per 70B layer): every MFMA pulls its 1 KiB B fragment
+  // from LDS, which pins the matrix pipe to the LDS rate with one wave per SIMD -- hence the register-tiled wide kernels above.
   const int step = 64;
   for (int t0 = tdone; t0 < T; t0 += step) {
     const int tn = min(step, T - t0);

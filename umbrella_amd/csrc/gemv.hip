@@ -212,7 +212,7 @@ __global__ __launch_bounds__(512) void gv_kernel(const u32x4* __restrict__ w, co
 #pragma unroll
       for (int r = 0; r < RW; r += 2) {
         const float g0 = rnd_prod<P>(val[r], iv), u0 = rnd_prod<P>(val[r + 1], iv);
-        act[(long)t * (N / 2) + ((n0 + r) >> 1)] = P::from_f(rnd<P>(g0 / (1.f + __expf(-g0))) * u0);
+        act[(long)t * (N / 2) + ((n0 + r) >> 1)] = P::from_f(silu_mul<P>(g0, u0));
       }
     } else {
       // GV_QKV: rows (2m, 2m+1) of a q / k head are RoPE partners (m, m + D/2) (model_utils.py:17-52, cache.py:53-65)

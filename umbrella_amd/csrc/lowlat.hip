@@ -338,7 +338,7 @@ __global__ __launch_bounds__(512, 2) void ll_gemm_kernel(const u32x4* __restrict
         const f32x4 v = acc[r][tt] * inv[tt];
         // rows are interleaved (gate_m, up_m); every step rounded to the model dtype as eager torch does (llama.py:107-110)
         const float g0 = rnd<P>(v[0]), u0 = rnd<P>(v[1]), g1 = rnd<P>(v[2]), u1 = rnd<P>(v[3]);
-        const float a0 = rnd<P>(g0 / (1.f + __expf(-g0))) * u0, a1 = rnd<P>(g1 / (1.f + __expf(-g1))) * u1;
+        const float a0 = silu_mul<P>(g0, u0), a1 = silu_mul<P>(g1, u1);
         *reinterpret_cast<unsigned*>(act + fm_off(t, (nt0 + r) * 8 + g * 2, TT)) = pack2<P>(a0, a1);
       }
     }

@@ -26,16 +26,9 @@
 #include <cstdlib>
 #include <type_traits>
 
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) char lds_char;
 typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
 typedef __attribute__((address_space(3))) unsigned lds_u32;
-
-__device__ __forceinline__ unsigned vg_and_or(unsigned a, unsigned mask, unsigned magic_v) {
-  unsigned r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(mask), "v"(magic_v));
-  return r;
-}
 
 #ifdef UMB_VGW_WNT
 #define VGW_WNT " nt"
@@ -175,41 +168,27 @@ __global__ __launch_bounds__(512) void vgemm_w_kernel(const u32x4* __restrict__ 
 
   // ---- operand state
   u32x4 raw[2];                                    // the wave's two int4 tiles of the current 128-k block (lane: row i, k-group g)
-  h2 s2[2], nz2[2], nz16_2[2];
+  DeqMeta dm[2];
   u32x4 wcur[2][2], wnext[2][2];                   // dequantised A fragments [n-tile][k32 half] of this / the next 64-k step
-  unsigned magic = 0x64006400u;
+  unsigned magic = F16::MAGIC;
   asm volatile("" : "+v"(magic));
-  const h2 sixteenth = {(_Float16)0.0625f, (_Float16)0.0625f};
   auto read_raw = [&](int kb) {
     const unsigned st = wst0 + (unsigned)(kb & 1) * VGW_WSTAGE;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       raw[q] = *reinterpret_cast<const lds_u32x4*>((size_t)(st + (unsigned)q * 1024u + (unsigned)lane * 16u));
-      const unsigned mm = *reinterpret_cast<const lds_u32*>((size_t)(st + 2048u + (unsigned)q * 64u + (unsigned)j * 4u));
-      const _Float16 sc = __builtin_bit_cast(_Float16, (u16)(mm & 0xffffu));
-      const _Float16 zf = __builtin_bit_cast(_Float16, (u16)(mm >> 16));
-      s2[q] = h2{sc, sc};
-      const _Float16 nz = -((_Float16)1024.0f + zf), nz16 = -((_Float16)64.0f + zf);
-      nz2[q] = h2{nz, nz};
-      nz16_2[q] = h2{nz16, nz16};
+      dm[q] = deq_meta(*reinterpret_cast<const lds_u32*>((size_t)(st + 2048u + (unsigned)q * 64u + (unsigned)j * 4u)));
     }
   };
   // one dword (two weights) of fragment (q, sx) of k64-half hf: exact fp16 dequant, W = fp16((code - zero) * scale)
   auto deq1 = [&](u32x4 (&dst)[2][2], int hf, int idx) {
     const int q = idx >> 3, sx = (idx >> 2) & 1, d = idx & 3;
     const unsigned w = raw[q][hf * 2 + sx];
-    const unsigned ws = (d & 2) ? (w >> 8) : w;
 #ifdef UMB_VGW_ABL_NODEQ      // ablation (wrong results): raw bits as the operand
-    dst[q][sx][d] = ws;
+    dst[q][sx][d] = (d & 2) ? (w >> 8) : w;
     return;
 #endif
-    if (d & 1) {
-      const h2 c = __builtin_bit_cast(h2, vg_and_or(ws, 0x00F000F0u, magic));
-      dst[q][sx][d] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(c, sixteenth, nz16_2[q]) * s2[q]);
-    } else {
-      const h2 c = __builtin_bit_cast(h2, vg_and_or(ws, 0x000F000Fu, magic));
-      dst[q][sx][d] = __builtin_bit_cast(unsigned, (c + nz2[q]) * s2[q]);
-    }
+    dst[q][sx][d] = deq_dword(w, d, dm[q], magic);
   };
 
   // B fragment (token tile tt, k32 half sx) of a ring slot: lane (j, g) reads row 16 tt + j, column 4 sx + g
@@ -305,33 +284,14 @@ __global__ __launch_bounds__(512) void vgemm_w_kernel(const u32x4* __restrict__ 
   vg_wait<0>();                                    // nothing of this wave may still be writing LDS when the workgroup retires
 #undef VGW_WAIT
 
-  // ---- epilogue (gemm.hip's): fp32 partials [S][T][N], or SiLU(gate) * up in the model dtype (S = 1, rows interleaved)
+  // ---- direct epilogue (gemm_fused.h): fp32 partials [S][T][N], or SiLU(gate) * up in the model dtype
 #pragma unroll
   for (int t = 0; t < TT; ++t) {
     const int tok = t0 + t * 16 + j;
     if (tok >= tend) continue;
-    float inv = 1.f;
-    if (fx.ssq_in) {
-      const float* sq = fx.ssq_in + (long)tok * (fx.ssq_stride ? fx.ssq_stride : fx.ssq_groups);
-      float a = 0.f;
-      for (int q = 0; q < fx.ssq_groups; q += 4) { const f32x4 v = *reinterpret_cast<const f32x4*>(sq + q); a += v[0]; a += v[1]; a += v[2]; a += v[3]; }
-      inv = rsqrtf(a / fx.ssq_dim + fx.eps);
-    }
+    const float inv = gemm_token_inv(fx, tok);
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      f32x4 v = acc[q][t];
-      const int ntile = nb * 16 + wv8 * 2 + q;
-      if (epi == EPI_SILU) {
-        v *= inv;
-        const float g0 = rnd<P>(v[0]), u0 = rnd<P>(v[1]), g1 = rnd<P>(v[2]), u1 = rnd<P>(v[3]);
-        const float a0 = rnd<P>(g0 / (1.f + __expf(-g0))) * u0, a1 = rnd<P>(g1 / (1.f + __expf(-g1))) * u1;
-        u16* act = reinterpret_cast<u16*>(out);
-        *reinterpret_cast<unsigned*>(act + (long)tok * (N / 2) + ntile * 8 + g * 2) = pack2<P>(a0, a1);
-      } else {
-        if (epi == EPI_ROUND) { v *= inv; v[0] = rnd<P>(v[0]); v[1] = rnd<P>(v[1]); v[2] = rnd<P>(v[2]); v[3] = rnd<P>(v[3]); }
-        *reinterpret_cast<f32x4*>(out + ((long)sp * T + tok) * N + ntile * 16 + g * 4) = v;
-      }
-    }
+    for (int q = 0; q < 2; ++q) gemm_store_direct<P>(acc[q][t], inv, epi, out, sp, T, tok, N, nb * 16 + wv8 * 2 + q, g);
   }
 }
 

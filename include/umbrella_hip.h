@@ -53,7 +53,23 @@ int umb_repack_dense(void* out, const void* w, int N, int K, int mode, int D, in
 int umb_awq_repack(void* outw, void* meta, const void* qweight, const void* qzeros, const void* scales,
                    int N, int K, int group, int mode, int D, int rope_heads, umb_stream_t stream);
 
+/* FP8 weight-only (W8A16) tensors: w8 [N][K] OCP float8_e4m3fn bytes in HF layout, scale fp32 [N][K/128] (the host expands
+ * per-tensor, per-channel and 128 x 128 block scales to this shape; W = e4m3(w8) * scale) -> FP8 tile order: 16 rows x 128 k
+ * = 2 KiB per tile (two 64-lane x 16 B wave loads), the four n-tiles of a block adjacent, [N/64][K/128][4] like the int4
+ * layout.  outw: N*K bytes, meta: (N/16)*(K/128)*64 bytes (16 fp32 scales per tile).  mode / D / rope_heads: the row maps of
+ * umb_repack_dense.  N % 64 == 0 and K % 128 == 0, else UMB_EINVAL.  NaN codes ((b & 0x7f) == 0x7f) are the loader's to
+ * refuse.  No reference counterpart (the reference loads dense and AutoAWQ checkpoints only). */
+int umb_fp8_repack(void* outw, void* meta, const void* w8, const void* scale, int N, int K, int mode, int D, int rope_heads,
+                   umb_stream_t stream);
+
 /* ------------------------------------------------------------------ linear layers */
+/* The `awq` argument of the calls below and UmbLinear.awq are a weight-FORMAT code: 0 dense 16-bit, 1 AutoAWQ int4
+ * (umb_awq_repack), 2 FP8 e4m3 (umb_fp8_repack).  Format 2: umb_gemm / umb_gemm_fused with epi 0, 1 and 2 and both dtypes
+ * (epi 3 / 4: UMB_EINVAL); every row count runs as launches of <= 64 rows of the skinny kernel, so a token's partials are
+ * the same bits at every T.  Arithmetic: per split slab, acc = fmaf(scale[n][g], G_g, acc) over the slab's 128-k groups g
+ * in ascending order, G_g the fp32 MFMA sum of e4m3(w8[n][k]) * x[t][k] over the group (the codes are exact in 16 bits).
+ * umb_gemm_ll refuses format 2; umb_gemv, the chain and umb_head_stream take 16-bit rows only.  The model forwards run
+ * format-2 layers on schedule 0 (ws->fused == 0, no chain / GEMV rows), resident, Llama and Qwen3; the lm_head stays 16-bit. */
 /* split plan for a [N][K] linear: depends on (N, K, format) only, never on T. */
 void umb_gemm_plan(int N, int K, int awq, int force_s1, int* R_out, int* S_out);
 /* the full plan: R n-tiles per wave, S K-splits, tb n-tiles per 4-wave block (4 R, or one less where that makes

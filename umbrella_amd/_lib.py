@@ -139,6 +139,7 @@ _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 SIGNATURES = {
     "umb_repack_dense": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "umb_awq_repack": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "umb_fp8_repack": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "umb_gemm_plan": [_I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I)],
     "umb_gemm_plan2": [_I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)],
     "umb_gemm_wide_split": [_I, _I, _I],

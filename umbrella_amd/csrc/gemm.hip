@@ -11,12 +11,16 @@
 //     that is directly the A operand of v_mfma_f32_16x16x32_{bf16,f16}
 //       dense : tile = 16 output rows x 32 k      (1 MFMA per tile)
 //       AWQ   : tile = 16 output rows x 128 k int4 (one AWQ group; 4 MFMAs per tile)
+//       FP8   : tile = 16 output rows x 128 k e4m3 bytes (2 KiB = two wave loads; one scale group; 4 MFMAs per tile)
 //   * weight rows are the MFMA M dimension, tokens the N dimension (<=16 per
 //     fragment): the matrix pipe does the MACs, VALU only unpacks nibbles.
 //   * AWQ: W = (q - z) * s is folded out of the MFMA.  The MFMA runs on the raw
 //     codes (q | magic -> bf16(128+q) / fp16(1024+q), 2 VALU ops per 2 codes);
 //     per 128-k group out += s * (acc - (z + magic) * sum_k x[k]) where sum_k x
 //     comes from one extra MFMA against a constant all-ones fragment.
+//   * FP8 (OCP e4m3fn, weight-only): every finite code is exact in fp16 and in bf16, so the A fragment is the converted
+//     codes themselves (v_cvt_pk_f32_fp8 + one pack per pair, no rounding) and the fp32 scale of the (row, 128-k group)
+//     is applied to the group's MFMA sum: acc = fmaf(scale, G_g, acc), groups in ascending k.
 //   * activations (<= 64 x K, L2 resident) are read straight into B fragments.
 //   * split-K writes fp32 partials [S][T][N]; the consumer kernel (epilogue.hip)
 //     reduces them in a fixed order -> results are bit-identical for any T
@@ -103,6 +107,32 @@ __global__ void repack_awq_kernel(const unsigned* __restrict__ qweight, const un
   }
 }
 
+// FP8 e4m3fn W[N][K] bytes (HF layout) + fp32 scale[N][K/128] -> tile order [N/64][K/128][4] of 2 KiB tiles.  A tile is two
+// wave loads: load h, lane (i, g) = the 8 bytes of row i at k = (2h) * 32 + 8g .. + 7 followed by those at (2h + 1) * 32 + 8g ..,
+// i.e. the A fragments of k32-steps 2h and 2h + 1 in byte form.  meta[tile] = the tile's 16 fp32 scales, packed-row order.
+__global__ void repack_fp8_kernel(const unsigned char* __restrict__ w8, const float* __restrict__ scale,
+                                  u32x4* __restrict__ outw, unsigned char* __restrict__ meta, int N, int K, int il, int D,
+                                  int rope_heads) {
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int KG = K / 128;
+  const long total = (long)(N / 16) * KG * 64;
+  if (gid >= total) return;
+  const int lane = gid & 63;
+  const long tile = gid >> 6;
+  const int kg = tile % KG, nt = tile / KG;
+  const int i = lane & 15, g = lane >> 4;
+  const int n = rowmap(nt * 16 + i, N, il, D, rope_heads);   // source row
+  const long otile = ((long)(nt >> 2) * KG + kg) * 4 + (nt & 3);
+  const unsigned char* src = w8 + (long)n * K + kg * 128 + g * 8;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const u32x2 lo = *reinterpret_cast<const u32x2*>(src + (2 * h) * 32);
+    const u32x2 hi = *reinterpret_cast<const u32x2*>(src + (2 * h + 1) * 32);
+    outw[(otile * 2 + h) * 64 + lane] = u32x4{lo[0], lo[1], hi[0], hi[1]};
+  }
+  if (g == 0) reinterpret_cast<float*>(meta + otile * 64)[i] = scale[(long)n * KG + kg];
+}
+
 // ------------------------------------------------------------------ main kernel
 // Block = 4 waves on the same K-slab; wave w owns n-tiles [(4*nb + w)*R, +R).  The activation
 // fragments of a CB x 128-k chunk are staged ONCE per block in LDS in fragment (lane-linear) order
@@ -113,9 +143,10 @@ __global__ void repack_awq_kernel(const unsigned* __restrict__ qweight, const un
 // AWQ modes: 0 dense 16-bit weights; 1 int4, dequant folded out of the MFMA (any activation dtype; the default for
 // launches of <= 64 rows); 2 int4 with exact fp16 dequant in registers, W = fp16((q - z) * s) -- bit-identical to what
 // awq_ext.dequantize_weights_cuda produces -- via v_pk_add_f16 / v_pk_mul_f16 (fp16 activations; wide launches; gemm_fused.h).
+// 3 (internal; format code 2 of the C interface): FP8 e4m3 bytes, two wave loads per tile, 16 fp32 scales per tile.
 template <typename P, int AWQ, int R> struct Stage {
-  u32x4 a[R][AWQ ? 1 : 4];
-  u32x4 m4[AWQ == 1 ? R : 1];     // folded path: 4 x {scale, zero} for output rows g*4 .. g*4+3
+  u32x4 a[R][AWQ == 3 ? 2 : AWQ ? 1 : 4];
+  u32x4 m4[(AWQ == 1 || AWQ == 3) ? R : 1];     // folded path: 4 x {scale, zero} for output rows g*4 .. g*4+3; FP8: their 4 fp32 scales
   unsigned m1[AWQ == 2 ? R : 1];  // exact path : {scale, zero} of this lane's weight row
 };
 
@@ -238,6 +269,48 @@ __device__ __forceinline__ void stage_compute(const Stage<P, AWQ, R>& st, const 
   }
 }
 
+// ---- FP8 e4m3 (OCP): two codes -> one dword of two fp16 / bf16 values.  v_cvt_pk_f32_fp8 is exact, and so is the step down to
+// 16 bits (every finite e4m3 value is a fp16 and a bf16 value): fp16 through v_cvt_pkrtz (nothing to truncate), bf16 as the
+// upper halves of the two floats (v_perm).  NaN codes never reach here: the loader refuses them.
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+template <typename P, bool HI> __device__ __forceinline__ unsigned fp8_pair(unsigned w) {
+  const f32x2 v = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, HI);
+  if constexpr (std::is_same<P, F16>::value) {
+    return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v[0], v[1]));
+  } else {
+    return __builtin_amdgcn_perm(__float_as_uint(v[1]), __float_as_uint(v[0]), 0x07060302u);
+  }
+}
+// Arithmetic of record: G_g = fp32 MFMA sum over the 128 k of group g of w8 * x; acc = fmaf(scale[n][g], G_g, acc), groups in
+// ascending order -- one fp32 FMA per group and output.
+template <typename P, int TT, int R>
+__device__ __forceinline__ void stage_compute_fp8(const Stage<P, 3, R>& st, const u32x4* xf, int lane, f32x4 (&acc)[R][TT]) {
+  u32x4 b[TT][4];
+#pragma unroll
+  for (int tt = 0; tt < TT; ++tt)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) b[tt][s] = xf[(tt * 4 + s) * 64 + lane];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    f32x4 ga[TT];
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) ga[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const unsigned d0 = st.a[r][s >> 1][(s & 1) * 2], d1 = st.a[r][s >> 1][(s & 1) * 2 + 1];
+      const u32x4 f = {fp8_pair<P, false>(d0), fp8_pair<P, true>(d0), fp8_pair<P, false>(d1), fp8_pair<P, true>(d1)};
+#pragma unroll
+      for (int tt = 0; tt < TT; ++tt) ga[tt] = P::mfma(f, b[tt][s], ga[tt]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float sc = __uint_as_float(st.m4[r][e]);
+#pragma unroll
+      for (int tt = 0; tt < TT; ++tt) acc[r][tt][e] = __builtin_fmaf(sc, ga[tt][e], acc[r][tt][e]);
+    }
+  }
+}
+
 // -DUMB_GEMM_TRACE (scripts/r3/gemm_trace.py builds a second library with it): wave 0 of every block stamps the constant
 // 100 MHz clock at its phase boundaries into fx.counters (16 x u64 per block; unused by the direct epilogues): 0 entry,
 // 1 prologue loads issued, 2 first x chunk staged, 3 first k-block computed, 4 main loop left, 5 stores drained,
@@ -298,6 +371,7 @@ __global__ __launch_bounds__(64 * NWV) void skinny_gemm_kernel(const u32x4* __re
     for (int tt = 0; tt < TT; ++tt) acc[r][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int nkb = kb1 - kb0;
+  constexpr unsigned WTILE = AWQ == 3 ? 2048u : 1024u;   // bytes of one packed (16-row, 128-k) tile: FP8 2 KiB, int4 1 KiB
   constexpr int PF = 2 * CB;                 // ring of PF weight stages: PF x R KiB-tiles in flight per wave
   // ---- streams.  Every load of the main loop is an unconditional buffer load: a k-block past the end of the slab, a
   // token row past T or the whole stream of a wave without tiles is OUT OF RANGE of its descriptor -> zeros, no fetch.
@@ -311,8 +385,8 @@ __global__ __launch_bounds__(64 * NWV) void skinny_gemm_kernel(const u32x4* __re
     const bool live = r < ntiles && nkb > 0;
     if (AWQ) {
       const long tile0 = ((long)(nt >> 2) * KB) * 4 + (nt & 3);        // tile order [N/64][K/128][4]
-      rw[r] = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4*>(wp + tile0 * 64), 0,
-                                                live ? (unsigned)(kb1 - 1) * 4096u + 1024u : 0u, 0x00020000);
+      rw[r] = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4*>(wp + tile0 * (WTILE / 16)), 0,
+                                                live ? (unsigned)(kb1 - 1) * (4u * WTILE) + WTILE : 0u, 0x00020000);
       rm[r] = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(meta + tile0 * 64), 0,
                                                 live ? (unsigned)(kb1 - 1) * 256u + 64u : 0u, 0x00020000);
     } else {
@@ -351,7 +425,11 @@ __global__ __launch_bounds__(64 * NWV) void skinny_gemm_kernel(const u32x4* __re
   auto sload = [&](Stage<P, AWQ, R>& sg, int kb) {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      if (AWQ) {
+      if (AWQ == 3) {
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2)
+          sg.a[r][AWQ == 3 ? h2 : 0] = __builtin_amdgcn_raw_buffer_load_b128(rw[r], lane * 16 + kb * 8192 + h2 * 1024, 0, 2);
+      } else if (AWQ) {
         // the k offset rides in the VGPR offset: that is the part of the address the range check certainly covers
         sg.a[r][0] = __builtin_amdgcn_raw_buffer_load_b128(rw[r], lane * 16 + kb * 4096, 0, 2);   // non-temporal
       } else {
@@ -416,10 +494,11 @@ __global__ __launch_bounds__(64 * NWV) void skinny_gemm_kernel(const u32x4* __re
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const unsigned char* mrec = ms + H * MSLOT + (kl * R + r) * 64;
-          if (AWQ == 1) sg.m4[r] = *reinterpret_cast<const u32x4*>(mrec + g * 16);
+          if (AWQ == 1 || AWQ == 3) sg.m4[r] = *reinterpret_cast<const u32x4*>(mrec + g * 16);
           if (AWQ == 2) sg.m1[r] = *reinterpret_cast<const unsigned*>(mrec + j * 4);
         }
-        stage_compute<P, AWQ, TT, R>(sg, xc + kl * TT * 4 * 64, lane, acc);
+        if constexpr (AWQ == 3) stage_compute_fp8<P, TT, R>(sg, xc + kl * TT * 4 * 64, lane, acc);
+        else stage_compute<P, AWQ, TT, R>(sg, xc + kl * TT * 4 * 64, lane, acc);
 #ifdef UMB_GEMM_TRACE
         if (c == 0 && kl == 0) { asm volatile("" :: "v"(acc[0][0][0])); UMB_STAMP(3); }
 #endif
@@ -522,6 +601,7 @@ __global__ __launch_bounds__(64 * NWV) void skinny_gemm_kernel(const u32x4* __re
     return;
   }
 
+  if constexpr (AWQ == 3) return;          // FP8: epi 0 / 1 / 2 only (umb_gemm_fused refuses 3 / 4)
   // ------------------------------------------------------------------ split epilogues (R == 1): publish, last arriver finishes
   if (S > 1) {
     if (active) {
@@ -1248,8 +1328,10 @@ extern "C" int umb_gemm_wide_split(int T, int N, int S_plan) {
 extern "C" void umb_gemm_plan(int N, int K, int awq, int force_s1, int* R_out, int* S_out) {
   const int NT = N / 16, KB = K / 128;
   int R = 1;
-  if (!awq && NT % 2 == 0 && NT >= 4096) R = 2;
-  if (awq && NT % 8 == 0 && NT >= 512) R = 2;      // two independent dequant chains per wave: +6-8 % measured
+  // format 2 (FP8, one byte per weight): the dense rule at half the bytes -- R as dense (one 2 KiB tile per wave and k-block
+  // is the dense tile's byte count over twice the k), and a slab keeps >= 512 k, the bytes of a dense slab of 256 k
+  if (awq != 1 && NT % 2 == 0 && NT >= 4096) R = 2;
+  if (awq == 1 && NT % 8 == 0 && NT >= 512) R = 2;      // two independent dequant chains per wave: +6-8 % measured
   int S = 1;
   if (!force_s1) {
     const int nblk = (NT + 4 * R - 1) / (4 * R);
@@ -1282,7 +1364,7 @@ extern "C" void umb_gemm_plan2(int N, int K, int awq, int force_s1, int* R_out, 
     if (b8 % 256 != 0 && b7 % 256 == 0) tb = 7;
     // exactly one 8-wave block of 14 tiles per CU: the CU's waves share ONE staged copy of the activations (two 4-wave
     // blocks each load their own: 6.6 KB of x per 14 KiB of weights and chunk); flag 0x80 = 8 waves per block
-    if (!no_w8 && awq && b8 % 256 != 0 && b14 == 256) tb = 14 | 0x80;
+    if (!no_w8 && awq == 1 && b8 % 256 != 0 && b14 == 256) tb = 14 | 0x80;
 
   }
   // Round 4: a linear that the rules above leave with at most ONE 4-wave block per CU (8B-AWQ gate/up: 256 blocks of 2 + 2 + 2 + 1
@@ -1372,7 +1454,7 @@ static int launch_tt(const void* wp, const void* meta, const u16* x, int ldx, fl
   // T > 64: the wide kernels where they apply; the rest (and every T <= 64) in skinny launches of 64 tokens
   const long ostride = (epi == EPI_SILU) ? (long)(N / 2) / 2 : (long)N;   // out rows in units of float
   int tdone = 0;
-  if constexpr (AWQ != 1) {
+  if constexpr (AWQ != 1 && AWQ != 3) {       // FP8: no wide kernel yet, 64-row launches below at every row count
     static const bool no_vgemm = getenv("UMB_NO_VGEMM") != nullptr;     // diagnostic: 64-token chunks only
     if (T > 64 && N % 128 == 0 && epi <= EPI_SILU && !no_vgemm) {
       // round 6: 32-row x whole-chunk waves, LDS-DMA activations (vgemm.hip); UMB_VGW=0: the kernels below
@@ -1444,6 +1526,8 @@ extern "C" int umb_gemm_fused(void* out, const void* x, int ldx, const void* wpa
   static const int tb_env = getenv("UMB_TB") ? atoi(getenv("UMB_TB")) : 0;     // experiments
   if (tb_env > 0) tb = tb_env;
   if (N % 16 || K % 128 || T < 1 || S < 1 || epi < 0 || epi > 4 || (epi == EPI_SILU && S != 1)) return UMB_EINVAL;
+  if (awq < 0 || awq > 2) return UMB_EINVAL;                             // 0 dense, 1 AutoAWQ int4, 2 FP8 e4m3
+  if (awq == 2 && (epi > EPI_SILU || !meta)) return UMB_EINVAL;          // FP8: raw / rounded partials and SiLU * up only
   if ((long)S * T * N * 4 >= (1L << 31)) return UMB_EINVAL;              // fp32 partials are stored through a 32-bit buffer offset
   if (awq && (N % 64 || (R != 1 && (N / 16) % 2))) return UMB_EINVAL;
   if ((tb & 0x7f) > ((tb & 0x80) ? 8 : 4) * R) tb = 0;
@@ -1474,6 +1558,9 @@ extern "C" int umb_gemm_fused(void* out, const void* x, int ldx, const void* wpa
   // W = fp16((q - z) * s) bit for bit, for EVERY row count -- one int4 arithmetic from the T = 1 row to the widest verify,
   // as the reference's single awq_ext kernel has (awq_utils.py:67-77).  Read per call (launch arguments are frozen into a
   // captured graph anyway), so a process can hold both forms.  The folded form exists for <= 64 rows only.
+  if (awq == 2) {
+    DISPATCH_DTYPE(dtype, { return launch_tt<P, 3>(wpacked, meta, (const u16*)x, ldx, (float*)out, T, N, K, R, S, epi, fx, st, tb); })
+  }
   const char* dq = getenv("UMB_DEQUANT");
   const bool awq_exact = (dq && dq[0] == 'e') || getenv("UMB_AWQ_EXACT") != nullptr;
   if (awq && dtype == UMB_F16 && (awq_exact || T > 64))
@@ -1512,6 +1599,20 @@ extern "C" int umb_awq_repack(void* outw, void* meta, const void* qweight, const
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
   hipLaunchKernelGGL(repack_awq_kernel, grid, block, 0, st, (const unsigned*)qweight, (const unsigned*)qzeros,
                      (const u16*)scales, (u32x4*)outw, (unsigned char*)meta, N, K, interleave, D, rope_heads);
+  UMB_LAUNCH_CHECK();
+  return UMB_OK;
+}
+
+// w8: [N][K] e4m3fn bytes (HF layout); scale: fp32 [N][K/128].  outw: N*K bytes; meta: (N/16)*(K/128)*64 bytes
+extern "C" int umb_fp8_repack(void* outw, void* meta, const void* w8, const void* scale, int N, int K, int mode, int D,
+                              int rope_heads, hipStream_t st) {
+  if (N < 64 || K < 128 || N % 64 || K % 128 || mode < 0 || mode > 2) return UMB_EINVAL;
+  if (mode == 1 && N % 2) return UMB_EINVAL;
+  if (mode == 2 && (D < 2 || D % 2 || rope_heads < 0 || (long)rope_heads * D > N)) return UMB_EINVAL;
+  const long total = (long)(N / 16) * (K / 128) * 64;
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  hipLaunchKernelGGL(repack_fp8_kernel, grid, block, 0, st, (const unsigned char*)w8, (const float*)scale, (u32x4*)outw,
+                     (unsigned char*)meta, N, K, mode, D, rope_heads);
   UMB_LAUNCH_CHECK();
   return UMB_OK;
 }

@@ -503,6 +503,7 @@ extern "C" int umb_gemm_ll(void* out, const void* x_fm, const void* wpacked, con
                            int awq, int epi, const UmbGemmLL* fx, int dtype, hipStream_t st) {
   if (N % 16 || K % 128 || T < 1 || T > 64 || !x_fm || !wpacked) return UMB_EINVAL;
   if (epi != LL_LOGITS && epi != LL_SILU && epi != LL_QKV && epi != LL_RESID) return UMB_EINVAL;
+  if (awq < 0 || awq > 1) return UMB_EINVAL;         // dense and AutoAWQ int4 only (FP8, format 2: umb_gemm_fused)
   if (awq && (N % 64 || !meta)) return UMB_EINVAL;
   LLArgs a = {};
   a.w = (const u32x4*)wpacked; a.meta = (const unsigned char*)meta; a.x = (const u32x4*)x_fm; a.out = out;

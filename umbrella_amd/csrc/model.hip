@@ -29,7 +29,8 @@ static inline int dbg_sync(const char* what, hipStream_t st) {
 // (70B o-proj, T = 13: S = 8 -> 4 costs the GEMM +0.4 us and saves the reduce 2.2 us; 70B down, K = 28672, keeps 8;
 // 8B-AWQ down keeps 8 of its planned 16).  A function of the layer shape only, like the plan itself.
 static inline int eff_s(const UmbLinear& l, int T, bool row_reduce = false) {
-  int S = umb_gemm_wide_split(T, l.N, l.S);
+  // FP8 (format 2) has no wide kernel: more than 64 rows run as 64-row launches of the skinny kernel, which keep the plan's S
+  int S = (l.awq == 2) ? l.S : umb_gemm_wide_split(T, l.N, l.S);
   if (row_reduce && T <= 64 && l.S_row > 0) return l.S_row;       // the plan's measured choice (umb_gemm_plan2)
   if (row_reduce && T <= 64) {
     const int cap = l.K / 1792 > 4 ? l.K / 1792 : 4;
@@ -43,6 +44,27 @@ static inline int lin(const UmbLinear& l, const void* x, int ldx, void* out, int
                       const UmbGemmFused* fx, bool row_reduce = false) {
   return umb_gemm_fused(out, x, ldx, l.w, l.meta, T, l.N, l.K, l.awq, eff_s(l, T, row_reduce), l.R | (l.tb << 8), epi, fx, dtype,
                         st);
+}
+
+// FP8 e4m3 linears (UmbLinear.awq == 2) run on schedule 0 only (layer_split / layer_split_defer), resident, one device; the
+// lm_head stays 16-bit.  fp8_layers: does the layer range hold one?  fp8_refused: ... in a forward that cannot run it.
+static inline bool fp8_layers(const UmbModel* m, const UmbStep* s) {
+  if (s->layer_begin < 0 || s->layer_end > m->L) return false;
+  for (int l = s->layer_begin; l < s->layer_end; ++l) {
+    const UmbLayer& x = m->layers[l];
+    if (x.qkv.awq == 2 || x.o.awq == 2 || x.gu.awq == 2 || x.down.awq == 2) return true;
+  }
+  return false;
+}
+static inline bool fp8_refused(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s) {
+  if (m->lm_head.awq == 2) return true;
+  if (!fp8_layers(m, s)) return false;
+  if (ws->fused != 0 || ws->chain_xchg) return true;
+  for (int l = s->layer_begin; l < s->layer_end; ++l) {
+    const UmbLayer& x = m->layers[l];
+    if (x.qkv.w_rows || x.o.w_rows || x.gu.w_rows || x.down.w_rows) return true;      // a GEMV workspace
+  }
+  return false;
 }
 
 // embedding (stage 0) / index resolution + hw = h * norm1_w and the per-64-column sums of squares of h
@@ -510,6 +532,7 @@ static int head(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, hip
 static int model_forward(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbTP* tp, hipStream_t st) {
   const int lb = s->layer_begin, le = s->layer_end;
   if (lb < 0 || le > m->L || lb >= le) return UMB_EINVAL;
+  if (fp8_refused(m, ws, s) || (tp_on(tp) && fp8_layers(m, s))) return UMB_EINVAL;
   if (tp_on(tp)) {
     // row-split partial sums meet between the GEMM and its reduce kernel: the 8-launch schedule only
     if (ws->fused != 0) return UMB_EINVAL;
@@ -667,6 +690,7 @@ extern "C" int umb_model_forward_offload(const UmbModel* m, const UmbWorkspace* 
                                          const UmbOffload* off, hipStream_t st) {
   const int lb = s->layer_begin, le = s->layer_end;
   if (lb < 0 || le > m->L || lb >= le) return UMB_EINVAL;
+  if (m->lm_head.awq == 2 || fp8_layers(m, s)) return UMB_EINVAL;      // FP8 linears: resident forwards only
   const bool ll = use_ll(m, ws, s);
   const int fm = ll ? 0 : split_fm_tt(m, ws, s, nullptr);
   const bool df = !ll && use_defer(m, ws, s, nullptr);
@@ -732,6 +756,7 @@ static int head_gemma2(const UmbModel* m, const UmbWorkspace* ws, const UmbStep*
 }
 
 static inline bool gemma2_ok(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbGemma2* g) {
+  if (m->lm_head.awq == 2 || fp8_layers(m, s)) return false;           // FP8 linears: Llama / Qwen3 forwards only
   return g && g->norms && ws->fused == 0 && s->layer_begin == 0 && s->layer_end == m->L && !s->skip_embed &&
          g->window >= 0 && (g->slide_parity == 0 || g->slide_parity == 1);
 }
@@ -765,6 +790,7 @@ static int qwen3_forward(const UmbModel* m, const UmbWorkspace* ws, const UmbSte
     return UMB_EINVAL;
   for (int l = 0; l < m->L; ++l)
     if (!q->norms[l].q_norm || !q->norms[l].k_norm) return UMB_EINVAL;
+  if (fp8_refused(m, ws, s) || (off && fp8_layers(m, s))) return UMB_EINVAL;
   const int fm = split_fm_tt(m, ws, s, nullptr);
   const bool df = use_defer(m, ws, s, nullptr);
   int sg = 4;

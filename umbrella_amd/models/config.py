@@ -38,6 +38,8 @@ class LlamaCfg:
     eos_token_id: list = field(default_factory=lambda: [128001, 128008, 128009])
     awq: bool = False                 # 4-bit AWQ (GEMM format, group 128, zero point)
     awq_group: int = 128
+    fp8: bool = False                 # FP8 e4m3 weight-only linears (W8A16; models/fp8_format.py); never together with awq
+    fp8_scheme: str = ""              # "block128" (*.weight_scale_inv) | "tensor" | "channel" (*.weight_scale)
     name: str = "llama"
     attention_bias: bool = False      # q/k/v projection bias (Qwen2: umbrella/models/qwen.py:94-96)
     embed_rows: int = 0               # rows of the embedding table when they differ from vocab_size (tensor-parallel shard:
@@ -50,6 +52,10 @@ class LlamaCfg:
     sliding_window: int = 0           # keys a sliding layer sees (p - c < window); 0 = every layer global
     sliding_parity: int = 0           # layer l slides when l % 2 == sliding_parity (Gemma-2: the even layers)
     hidden_activation: str = "silu"   # MLP gate: "silu" or "gelu_pytorch_tanh"
+
+    def __post_init__(self):
+        if self.awq and self.fp8:
+            raise ValueError(f"'{self.name}': awq and fp8 are mutually exclusive weight formats")
 
     @property
     def q_dim(self):
@@ -78,7 +84,12 @@ class LlamaCfg:
             with open(gen) as f:
                 eos = json.load(f).get("eos_token_id", eos)
         q = c.get("quantization_config") or {}
+        from .fp8_format import parse_quant_config
+        fp8_scheme = parse_quant_config(q)          # None: not an FP8 checkpoint; ValueError: an FP8 form that is not computed
         if c.get("model_type") == "gemma2":
+            if fp8_scheme:
+                raise NotImplementedError("FP8 checkpoints are not supported for Gemma-2 (quantization_config.quant_method = "
+                                          f"{q.get('quant_method')!r})")
             return cls._gemma2_from_dict(c, eos, q, path)
         if c.get("model_type") == "qwen3_moe":
             raise NotImplementedError("Qwen3-MoE (model_type 'qwen3_moe') is not supported: dense Qwen3 only")
@@ -103,6 +114,7 @@ class LlamaCfg:
                    tie_word_embeddings=c.get("tie_word_embeddings", False),
                    eos_token_id=eos if isinstance(eos, list) else [eos],
                    awq=q.get("quant_method") == "awq", awq_group=q.get("group_size", 128),
+                   fp8=bool(fp8_scheme), fp8_scheme=fp8_scheme or "",
                    name=os.path.basename(os.path.normpath(path)))
 
     @classmethod
@@ -242,11 +254,12 @@ KNOWN["google/gemma-2-9b-it"] = _gemma2(3584, 14336, 42, 16, 8, 256, 256, "gemma
 KNOWN["google/gemma-2-27b-it"] = _gemma2(4608, 36864, 46, 32, 16, 128, 144, "gemma-2-27b-it")
 
 
-def _qwen3(H, I, L, Hq, Hkv, tie, awq=False, name="qwen3"):
+def _qwen3(H, I, L, Hq, Hkv, tie, awq=False, name="qwen3", fp8=False):
     return LlamaCfg(family="qwen3", vocab_size=151936, hidden_size=H, intermediate_size=I, num_hidden_layers=L,
                     num_attention_heads=Hq, num_key_value_heads=Hkv, head_dim=128, rms_norm_eps=1e-6, rope_theta=1000000.0,
                     rope_scaling=None, max_position_embeddings=40960, tie_word_embeddings=tie,
-                    eos_token_id=[151645, 151643], awq=awq, attention_bias=False, name=name)
+                    eos_token_id=[151645, 151643], awq=awq, attention_bias=False, name=name, fp8=fp8,
+                    fp8_scheme="block128" if fp8 else "")
 
 
 # Qwen3 dense checkpoints (not in the reference's registry; HF Qwen3ForCausalLM defines them): public dims, head_dim 128 free
@@ -258,6 +271,15 @@ for _size, _d in _QWEN3_DIMS.items():
     KNOWN[f"Qwen/Qwen3-{_size}"] = _qwen3(*_d, name=f"qwen3-{_size.lower()}")
     if _size in ("4B", "8B", "14B", "32B"):
         KNOWN[f"Qwen/Qwen3-{_size}-AWQ"] = _qwen3(*_d, awq=True, name=f"qwen3-{_size.lower()}-awq")
+    # FP8 e4m3 builds with 128 x 128 block scales.  Ids and dims unverified here (no hub access); a local directory's
+    # config.json is the contract
+    KNOWN[f"Qwen/Qwen3-{_size}-FP8"] = _qwen3(*_d, fp8=True, name=f"qwen3-{_size.lower()}-fp8")
+# compressed-tensors FP8 builds of the Llama 3.x instruct models (per-channel weight scales), dims of their dense entries;
+# ids unverified here as well
+for _name, _dims in (("RedHatAI/Meta-Llama-3.1-8B-Instruct-FP8-dynamic", _L8), ("RedHatAI/Meta-Llama-3.1-70B-Instruct-FP8-dynamic", _L70),
+                     ("RedHatAI/Llama-3.3-70B-Instruct-FP8-dynamic", _L70)):
+    KNOWN[_name] = _l(**_dims, rope_scaling=LLAMA31_ROPE, fp8=True, fp8_scheme="channel",
+                      name=_name.split("/")[1].lower())
 
 
 def rope_inv_freq(cfg: LlamaCfg) -> tuple[torch.Tensor, float]:

@@ -37,6 +37,8 @@ class Gemma2(Llama):
         c = self.config
         if c.awq:
             raise NotImplementedError("AWQ Gemma-2 checkpoints are not supported")
+        if c.fp8:
+            raise NotImplementedError("FP8 Gemma-2 checkpoints are not supported")
         if c.hidden_activation not in ("gelu_pytorch_tanh", "gelu_tanh"):
             raise NotImplementedError(f"Gemma-2 MLP activation {c.hidden_activation!r} (only gelu_pytorch_tanh)")
         self.sched, self.fused = "split", False

@@ -26,7 +26,8 @@ from .._lib import UmbLayer, UmbLinear, UmbModel, UmbOffload, UmbStep, UmbWorksp
 from ..attn.cache import TreeKVCache
 from .base import LLMBase
 from .config import KNOWN, LlamaCfg, require_family, rope_tables
-from .synthetic import LINEARS, linear_shapes, synth_awq_tensors, synth_tensor
+from . import fp8_format
+from .synthetic import LINEARS, linear_shapes, synth_awq_tensors, synth_fp8_tensors, synth_tensor
 from ..logging_config import setup_logger
 
 logger = setup_logger()
@@ -49,7 +50,8 @@ def _align(n, a=256):
 CHAIN_TMAX = 4        # include/umbrella_hip.h UMB_CHAIN_TMAX: the persistent chain's exchange layout is fixed at 4 rows
 
 class PackedLinear:
-    """One linear layer in MFMA tile order (dense 16-bit or AWQ int4)."""
+    """One linear layer in MFMA tile order.  ``awq`` is the weight-format code of the C interface: 0 dense 16-bit,
+    1 AutoAWQ int4, 2 FP8 e4m3 (True / False keep meaning int4 / dense)."""
 
     def __init__(self, N, K, awq, w, meta, force_s1=False):
         self.N, self.K, self.awq, self.w, self.meta = N, K, int(awq), w, meta
@@ -64,9 +66,19 @@ class PackedLinear:
 
     @staticmethod
     def packed_bytes(N, K, awq):
+        """(weight bytes, metadata bytes) of the packed form, each rounded up to 256; awq: the format code"""
+        if int(awq) == 2:
+            return _align(N * K), _align((N // 16) * (K // 128) * 64)
         if awq:
             return _align(N * K // 2), _align((N // 16) * (K // 128) * 64)
         return _align(N * K * 2), 0
+
+    @staticmethod
+    def raw_bytes(N, K, awq):
+        """(weight bytes, metadata bytes) the repack kernels write (no rounding)"""
+        fmt = int(awq)
+        meta = (N // 16) * (K // 128) * 64 if fmt else 0
+        return (N * K if fmt == 2 else N * K // 2 if fmt else N * K * 2), meta
 
     @classmethod
     def from_dense(cls, w: torch.Tensor, out=None, force_s1=False, interleave=False, rope=None):
@@ -96,6 +108,22 @@ class PackedLinear:
                   scales.to(torch.float16).contiguous(), N, K, group, *((1, 0, 0) if interleave else
                                                                          ((2, rope[0], rope[1]) if rope else (0, 0, 0))))
         lin = cls(N, K, True, w, meta, force_s1=interleave)
+        lin.interleaved, lin.rope = bool(interleave), rope
+        return lin
+
+    @classmethod
+    def from_fp8(cls, w8, scale_rows, out_w=None, out_meta=None, interleave=False, rope=None):
+        """FP8 e4m3 weight-only linear.  w8 [N, K] uint8 / float8_e4m3fn codes (HF layout) and scale_rows fp32 [N, K/128]
+        (fp8_format.expand_scale), both on the GPU; interleave / rope as in from_dense."""
+        N, K = w8.shape
+        assert N % 64 == 0 and K % 128 == 0, (N, K)
+        assert tuple(scale_rows.shape) == (N, K // 128) and scale_rows.dtype == torch.float32, (tuple(scale_rows.shape), N, K)
+        wb, mb = cls.packed_bytes(N, K, 2)
+        w = out_w if out_w is not None else torch.empty(wb, dtype=torch.uint8, device=w8.device)
+        meta = out_meta if out_meta is not None else torch.empty(mb, dtype=torch.uint8, device=w8.device)
+        _lib.call("umb_fp8_repack", w, meta, w8.contiguous().view(torch.uint8), scale_rows.contiguous(), N, K,
+                  *((1, 0, 0) if interleave else ((2, rope[0], rope[1]) if rope else (0, 0, 0))))
+        lin = cls(N, K, 2, w, meta, force_s1=interleave)
         lin.interleaved, lin.rope = bool(interleave), rope
         return lin
 
@@ -218,6 +246,13 @@ class Llama(LLMBase):
             raise ValueError(f"Model type '{model_name}' is not supported. Supported types: {list(KNOWN.keys())} "
                              "or a local directory with config.json")
         require_family(self.config, self.FAMILY, type(self).__name__)
+        if self.config.fp8:
+            # FP8 linears exist on the split schedule only (csrc/model.hip): no fused / low-latency / GEMV / chain forms
+            if offload:
+                raise NotImplementedError(f"offload=True is not supported for FP8 checkpoints ('{self.config.name}')")
+            if self.fused or self.sched not in ("auto", "split"):
+                logger.info(f"'{self.config.name}' is an FP8 checkpoint: UMB_SCHED / UMB_FUSED are ignored (split schedule)")
+            self.sched, self.fused = "split", False
         if self.sched == "auto":
             self.sched = "split" if (self.config.awq or self.config.hidden_size >= 4096) else "ll"
         c = self.config
@@ -244,6 +279,9 @@ class Llama(LLMBase):
                 with safe_open(f, "pt") as h:
                     for k in h.keys():
                         index[k] = f
+                    if c.fp8 and "lm_head.weight" in h.keys():          # an FP8 head is refused before anything is loaded
+                        fp8_format.check_head({k for k in h.keys() if k.startswith("lm_head.")},
+                                              lambda k: h.get_slice(k).get_dtype())
 
             def fetch(name, shape, kind):
                 if name == "lm_head.weight" and name not in index:
@@ -285,10 +323,28 @@ class Llama(LLMBase):
         K = shapes[names[0]][1]
         il = names[0] == "mlp.gate_proj" and self.INTERLEAVE_GU   # fused [gate; up]: interleave rows, SiLU*up in the GEMM epilogue
         rope = (c.head_dim, c.num_attention_heads + c.num_key_value_heads) if names[0] == "self_attn.q_proj" else None
-        wb, mb = PackedLinear.packed_bytes(N, K, c.awq)
-        w_view = slab[cursor:cursor + (N * K // 2 if c.awq else N * K * 2)]
-        meta_view = slab[cursor + wb:cursor + wb + (N // 16) * (K // 128) * 64] if c.awq else None
-        if c.awq:
+        fmt = 2 if c.fp8 else int(c.awq)
+        wb, mb = PackedLinear.packed_bytes(N, K, fmt)
+        rw, rm = PackedLinear.raw_bytes(N, K, fmt)
+        w_view = slab[cursor:cursor + rw]
+        meta_view = slab[cursor + wb:cursor + wb + rm] if fmt else None
+        if c.fp8:
+            parts = []
+            for n in names:
+                base = prefix + n
+                if getattr(fetch, "gen", None) is not None:
+                    std = 0.02 * (fetch.resid_scale if n in ("self_attn.o_proj", "mlp.down_proj") else 1.0)
+                    w8, sc = synth_fp8_tensors(shapes[n][0], K, c.fp8_scheme or "block128", self.device, fetch.gen, std)
+                else:
+                    w8 = fetch(base + ".weight", shapes[n], "q")
+                    sc = fetch(base + fp8_format.SCALE_SUFFIX[c.fp8_scheme], None, "q")
+                codes = fp8_format.check_weight(base + ".weight", w8)
+                assert tuple(codes.shape) == tuple(shapes[n]), (base, tuple(codes.shape), shapes[n])
+                parts.append((codes, fp8_format.expand_scale(sc, shapes[n][0], K, base + fp8_format.SCALE_SUFFIX[c.fp8_scheme])
+                              .to(self.device)))
+            codes, rows = fp8_format.stack(parts)
+            lin = PackedLinear.from_fp8(codes, rows, out_w=w_view, out_meta=meta_view, interleave=il, rope=rope)
+        elif c.awq:
             parts = []
             for n in names:
                 base = prefix + n
@@ -316,11 +372,14 @@ class Llama(LLMBase):
         if self.fused:
             lin.R, lin.tb, lin.S_row = 1, 0, 0      # the in-kernel split epilogues own one n-tile per wave (ws.fused == 1
                                                    # whenever self.fused is set, whatever `sched` says: see reserve())
-        lin.off_w, lin.off_meta = cursor, (cursor + wb if c.awq else None)
+        lin.off_w, lin.off_meta = cursor, (cursor + wb if fmt else None)
         return lin, cursor + wb + mb
 
     def alloc(self, **kwargs):
         c, dev, dt = self.config, self.device, self.dtype
+        if c.fp8 and (kwargs.get("layer_range") is not None or self._tp is not None):
+            raise NotImplementedError(f"FP8 checkpoints ('{c.name}') run resident on one GPU: no layer pipelining, no "
+                                      "tensor parallelism")
         _lib.load()
         exit_layer = kwargs.pop("exit_layer", -1)
         self.num_cache_layers = kwargs.get("num_cache_layers", 0)
@@ -349,7 +408,10 @@ class Llama(LLMBase):
                 # embedding) -- an untied last stage then got the embedding's values as its head, i.e. another model
                 # than the one GPU runs (found with the tiny untied pair: the sharded run repeated its input token)
                 reseed.manual_seed(self._seed * 1000003 + 500009)
-            head_w = self.embed_tokens if c.tie_word_embeddings else fetch("lm_head.weight", (V, H), "head")[:V].to(dt)
+            head_w = self.embed_tokens if c.tie_word_embeddings else fetch("lm_head.weight", (V, H), "head")
+            if "float8" in str(head_w.dtype):
+                raise ValueError("lm_head.weight: an FP8 lm_head is not supported (the head must be a 16-bit tensor)")
+            head_w = head_w[:V].to(dt)
             assert head_w.shape == (V, H), (tuple(head_w.shape), V, H)
             self.lm_head = PackedLinear.from_dense(head_w, force_s1=True)
             assert self.lm_head.N == V
@@ -369,7 +431,7 @@ class Llama(LLMBase):
         shapes = linear_shapes(c)
         slab_bytes = 0
         for _, names in groups:
-            wb, mb = PackedLinear.packed_bytes(sum(shapes[n][0] for n in names), shapes[names[0]][1], c.awq)
+            wb, mb = PackedLinear.packed_bytes(sum(shapes[n][0] for n in names), shapes[names[0]][1], 2 if c.fp8 else int(c.awq))
             slab_bytes += wb + mb
         self.slab_bytes = slab_bytes
         # host side of the offload path: ONE arena on the GPU's NUMA node, pinned with one registration (models/host_arena.py;
@@ -479,7 +541,10 @@ class Llama(LLMBase):
         kernels (csrc/gemv.hip) wherever alloc() kept row-major weight copies; off: every T <= 64 forward of this
         model takes ONE shape-only kernel path, which is what makes a token's logits independent of how many rows
         share its launch (the batch invariance greedy spec == greedy AR rests on).  Changes launch arguments: call
-        before any graph capture."""
+        before any graph capture.  FP8 models: a no-op (no GEMV / chain form of the FP8 linears)."""
+        if self.config.fp8:
+            self.gemv = False
+            return
         for i, lins in enumerate(self.layers):
             for key, ln in lins.items():
                 ln.gemv_on = bool(on)
@@ -752,5 +817,5 @@ class Llama(LLMBase):
         per_layer = 0
         for lins in self.layers[:1]:
             for ln in lins.values():
-                per_layer += (ln.N * ln.K // 2 + (ln.N // 16) * (ln.K // 128) * 64) if ln.awq else ln.N * ln.K * 2
+                per_layer += sum(PackedLinear.raw_bytes(ln.N, ln.K, ln.awq))
         return per_layer * self.num_layers + (self.lm_head.N * self.lm_head.K * 2 if self.lm_head is not None else 0)

@@ -96,3 +96,15 @@ def synth_awq_tensors(N: int, K: int, group: int, device, gen: torch.Generator, 
     qzeros = torch.randint(-2**31, 2**31 - 1, (K // group, N // 8), dtype=torch.int32, device=device, generator=gen)
     scales = (torch.rand((K // group, N), device=device, generator=gen) * 0.5 + 0.75) * (std / 6.5)
     return qweight, qzeros, scales.to(torch.float16)
+
+
+def synth_fp8_tensors(N: int, K: int, scheme: str, device, gen: torch.Generator, std: float = 0.02):
+    """Full-size random FP8 (OCP e4m3fn, weight-only) linear straight on ``device``: (weight float8_e4m3fn [N, K], scale in
+    the checkpoint shape of ``scheme`` -- "block128": fp32 [ceil(N/128), K/128]; "channel": [N, 1]; "tensor": [1]).  Codes are
+    uniform over the e4m3 values of magnitude <= 1.875 (no NaN codes), whose rms is ~0.60; scales ~ std / 0.60."""
+    codes = torch.randint(0, 64, (N, K), dtype=torch.int32, device=device, generator=gen)          # |value| in [0, 1.875)
+    sign = torch.randint(0, 2, (N, K), dtype=torch.int32, device=device, generator=gen) << 7
+    w8 = (codes | sign).to(torch.uint8).view(torch.float8_e4m3fn)
+    shape = {"block128": ((N + 127) // 128, K // 128), "channel": (N, 1), "tensor": (1,)}[scheme]
+    scale = (torch.rand(shape, device=device, generator=gen) * 0.5 + 0.75) * (std / 0.60)
+    return w8, scale.to(torch.float32)

@@ -360,6 +360,8 @@ def build_pipelined_engine(device: str, dtype=torch.float16, seed: int = 0, **co
     from .speculation.static_speculation_engine import resolve_growmap_path
     t = config.get("model")
     require_family(KNOWN[t] if t in KNOWN else LlamaCfg.from_dir(t), "llama", "layer pipelining")
+    if (KNOWN[t] if t in KNOWN else LlamaCfg.from_dir(t)).fp8:
+        raise NotImplementedError(f"layer pipelining is not supported for FP8 checkpoints ('{t}')")
     kind = config.pop("engine", "static")
     assert kind in ("static", "dynamic"), kind
     rank, world = dist.get_rank(), dist.get_world_size()

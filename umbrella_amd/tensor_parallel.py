@@ -279,6 +279,8 @@ class TensorParallelLlama:
 
     def __init__(self, cfg: LlamaCfg, shard, comm: TPComm, force_hook: bool = False):
         import ctypes as C
+        if getattr(cfg, "fp8", False) or getattr(shard.config, "fp8", False):
+            raise NotImplementedError(f"tensor parallelism is not supported for FP8 checkpoints ('{cfg.name}')")
         self.config, self.m, self.comm = cfg, shard, comm
         self.world, self.rank = comm.world, comm.rank
         self.device, self.dtype, self.max_length = shard.device, shard.dtype, shard.max_length
@@ -337,6 +339,8 @@ class TensorParallelLlama:
         from .models.config import require_family
         from .models.llama import Llama
         require_family(cfg, "llama", "tensor parallelism")
+        if cfg.fp8:
+            raise NotImplementedError(f"tensor parallelism is not supported for FP8 checkpoints ('{cfg.name}')")
         lc = local_config(cfg, comm.world)
         sd = dict(shard_state_dict(source, cfg, comm.rank, comm.world)) if isinstance(source, dict) else source
         m = Llama(f"{name}-tp{comm.rank}of{comm.world}", max_length=max_length, device=device, dtype=dtype, state_dict=sd,

@@ -12,15 +12,17 @@
 #include <cstdio>
 
 // UMB_DEBUG_SYNC=1: synchronise after every launch and name the first one that fails (eager launches only)
-static inline int dbg_sync(const char* what, hipStream_t st) {
+static inline bool dbg_sync_on() {
   static const bool on = getenv("UMB_DEBUG_SYNC") != nullptr;
-  if (!on) return 0;
+  return on;
+}
+static int dbg_sync(const char* what, hipStream_t st) {
   const hipError_t e = hipStreamSynchronize(st);
   if (e != hipSuccess) { fprintf(stderr, "[umb] %s failed: %s\n", what, hipGetErrorString(e)); return UMB_EHIP; }
   fprintf(stderr, "[umb] ok %s\n", what);
   return 0;
 }
-#define CK(x) do { int rc__ = (x); if (rc__) return rc__; rc__ = dbg_sync(#x, st); if (rc__) return rc__; } while (0)
+#define CK(x) do { int rc__ = (x); if (rc__) return rc__; if (dbg_sync_on()) { rc__ = dbg_sync(#x, st); if (rc__) return rc__; } } while (0)
 
 // split count actually used: the plan's S (a function of the layer shape only, so T <= 64 results are batch
 // invariant); the wide verify (T > 64) takes the S <= plan that fills the verify kernel's block slots once (gemm.hip)
@@ -46,20 +48,25 @@ static inline int lin(const UmbLinear& l, const void* x, int ldx, void* out, int
                         st);
 }
 
-// FP8 e4m3 linears (UmbLinear.awq == 2) run on schedule 0 only (layer_split / layer_split_defer), resident, one device; the
-// lm_head stays 16-bit.  fp8_layers: does the layer range hold one?  fp8_refused: ... in a forward that cannot run it.
+// ---- validation, shared by every entry point
+static inline bool range_ok(const UmbModel* m, const UmbStep* s) {
+  return s->layer_begin >= 0 && s->layer_end <= m->L && s->layer_begin < s->layer_end;
+}
+// FP8 e4m3 linears (UmbLinear.awq == 2) run on schedule 0 only (layer_split), resident, one device, Llama and Qwen3; the
+// lm_head stays 16-bit.  fp8_layers: does the layer range hold one?  fp8_refused: ... in a forward that cannot run it;
+// plain: a resident forward on one device of a family that takes FP8 layers at all.
 static inline bool fp8_layers(const UmbModel* m, const UmbStep* s) {
-  if (s->layer_begin < 0 || s->layer_end > m->L) return false;
+  if (!range_ok(m, s)) return false;
   for (int l = s->layer_begin; l < s->layer_end; ++l) {
     const UmbLayer& x = m->layers[l];
     if (x.qkv.awq == 2 || x.o.awq == 2 || x.gu.awq == 2 || x.down.awq == 2) return true;
   }
   return false;
 }
-static inline bool fp8_refused(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s) {
+static inline bool fp8_refused(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, bool plain) {
   if (m->lm_head.awq == 2) return true;
   if (!fp8_layers(m, s)) return false;
-  if (ws->fused != 0 || ws->chain_xchg) return true;
+  if (!plain || ws->fused != 0 || ws->chain_xchg) return true;
   for (int l = s->layer_begin; l < s->layer_end; ++l) {
     const UmbLayer& x = m->layers[l];
     if (x.qkv.w_rows || x.o.w_rows || x.gu.w_rows || x.down.w_rows) return true;      // a GEMV workspace
@@ -67,19 +74,77 @@ static inline bool fp8_refused(const UmbModel* m, const UmbWorkspace* ws, const 
   return false;
 }
 
-// embedding (stage 0) / index resolution + hw = h * norm1_w and the per-64-column sums of squares of h
-static int prologue(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const void* first_norm, hipStream_t st,
-                    int fm_tt = 0) {
-  if (s->T < 1 || s->T > ws->Tmax) return UMB_EINVAL;
-  if (ws->fused != 1) {
-    CK(umb_embed_prep(ws->h, s->skip_embed ? nullptr : m->embed, m->H, s->T, s->tokens, s->positions, s->slots,
-                      s->prefix_len, s->tokens_all, s->n_ptr, s->tree_off, s->depth, ws->pos, ws->slot, ws->prefix,
-                      nullptr, nullptr, nullptr, 0, m->dtype, st));
-    return umb_rmsnorm_fm(ws->xn, ws->h, first_norm, m->eps, s->T, m->H, fm_tt, m->dtype, st);
-  }
-  return umb_embed_prep(ws->h, s->skip_embed ? nullptr : m->embed, m->H, s->T, s->tokens, s->positions, s->slots,
-                        s->prefix_len, s->tokens_all, s->n_ptr, s->tree_off, s->depth, ws->pos, ws->slot, ws->prefix,
-                        ws->hw, first_norm, ws->ssq, ws->ssq_stride, m->dtype, st);
+// ---- operands and calls every schedule shares
+// the K and V^T slabs of layer l
+struct KV { char* k; char* vt; };
+static inline KV kv_slabs(const UmbModel* m, int l) {
+  const size_t esz = 2;
+  return {(char*)m->k_cache + (size_t)l * m->Hkv * m->Lmax * m->D * esz,
+          (char*)m->vt_cache + (size_t)l * m->Hkv * VT_LD(m->Lmax) * m->D * esz};
+}
+// the norm weight the residual reduce behind layer l folds in: the next layer's input norm, the final norm behind the last
+// layer of the model, nothing at the end of an earlier pipeline stage
+static inline const void* next_norm_of(const UmbModel* m, int l, int le) {
+  return (l + 1 < le) ? m->layers[l + 1].norm1 : (le == m->L ? m->final_norm : nullptr);
+}
+static inline bool rows_ok(const UmbWorkspace* ws, const UmbStep* s) { return s->T >= 1 && s->T <= ws->Tmax; }
+// embedding (stage 0) / index resolution; with hw / norm_w / ssq also hw = h * norm_w and the per-64-column sums of squares of h.
+// fm >= 0: umb_embed_prep_fm with that many token tiles of an FM-ordered hw (0: row-major); fm < 0: umb_embed_prep
+static int embed(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, void* hw, const void* norm_w, float* ssq, int fm,
+                 hipStream_t st) {
+  if (!rows_ok(ws, s)) return UMB_EINVAL;
+  const void* table = s->skip_embed ? nullptr : m->embed;
+  const int stride = ssq ? ws->ssq_stride : 0;
+  if (fm < 0)
+    return umb_embed_prep(ws->h, table, m->H, s->T, s->tokens, s->positions, s->slots, s->prefix_len, s->tokens_all, s->n_ptr,
+                          s->tree_off, s->depth, ws->pos, ws->slot, ws->prefix, hw, norm_w, ssq, stride, m->dtype, st);
+  return umb_embed_prep_fm(ws->h, table, m->H, s->T, s->tokens, s->positions, s->slots, s->prefix_len, s->tokens_all, s->n_ptr,
+                           s->tree_off, s->depth, ws->pos, ws->slot, ws->prefix, hw, norm_w, ssq, stride, fm, m->dtype, st);
+}
+// tree attention (+ split merge) of one layer.  fm >= 0: umb_tree_attn2, output in FM order with that many token tiles
+// (0: row-major); fm < 0: umb_tree_attn
+static int tree_attn(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const KV& kv, int fm, hipStream_t st) {
+  if (fm < 0)
+    return umb_tree_attn(ws->attn, ws->q, kv.k, kv.vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
+                         s->n_mask_keys, s->T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_chunk, ws->attn_splits, m->attn_scale,
+                         ws->attn_counters, m->dtype, st);
+  return umb_tree_attn2(ws->attn, ws->q, kv.k, kv.vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
+                        s->n_mask_keys, s->T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_chunk, ws->attn_splits, m->attn_scale,
+                        ws->attn_counters, fm, m->dtype, st);
+}
+// "the consumer applies 1 / rms": the GEMM ran on hw = h * w and scales its outputs by rsqrt(sum of the producer's `groups` sums
+// of squares / H + eps).  stride: row stride of ws->ssq as the kernel is told it (0: the groups are packed, schedule 1);
+// row0: first token row (head_from)
+static inline void rms_from_ssq(UmbGemmFused& f, const UmbModel* m, const UmbWorkspace* ws, int groups, int stride, int row0 = 0) {
+  f.ssq_in = ws->ssq + (size_t)row0 * ws->ssq_stride; f.ssq_groups = groups; f.pad0 = stride; f.ssq_dim = (float)m->H; f.eps = m->eps;
+}
+static inline void rms_from_ssq(UmbGemmLL& f, const UmbModel* m, const UmbWorkspace* ws, int groups) {
+  f.ssq_in = ws->ssq; f.ssq_groups = groups; f.ssq_in_stride = ws->ssq_stride; f.ssq_dim = (float)m->H; f.eps = m->eps;
+}
+// epi 3 of the low-latency / GEMV kernels: (+bias), RoPE at the tree positions, q out, K / V appended at their slots
+static inline void qkv_epilogue(UmbGemmLL& f, const UmbModel* m, const UmbWorkspace* ws, const KV& kv, const void* bias) {
+  f.pos = ws->pos; f.slot = ws->slot; f.cosT = m->rope_cos; f.sinT = m->rope_sin; f.q_out = ws->q; f.k_cache = kv.k;
+  f.vt_cache = kv.vt; f.bias = bias; f.Hq = m->Hq; f.Hkv = m->Hkv; f.D = m->D; f.Lmax = m->Lmax;
+}
+// epi 4 of the same: h += out ; hw = h * norm_w ; sums of squares
+static inline void resid_epilogue(UmbGemmLL& f, const UmbWorkspace* ws, const void* norm_w) {
+  f.h = ws->h; f.hw = ws->hw; f.norm_w = norm_w; f.ssq_out = ws->ssq; f.ssq_out_stride = ws->ssq_stride;
+}
+// lm_head over rows [head_from, T) of the normed residual ws->xn
+static int head_xn(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, hipStream_t st) {
+  if (s->head_from >= s->T) return UMB_OK;
+  const char* xn = (const char*)ws->xn + (size_t)s->head_from * m->H * 2;
+  return lin(m->lm_head, xn, m->H, ws->logits, s->T - s->head_from, m->dtype, st, /*EPI_ROUND*/1, nullptr);
+}
+// ... of ws->hw = h * final norm weight, 1 / rms from `groups` sums of squares per token (stride as rms_from_ssq; x_fm: hw is in
+// FM order, head_from == 0)
+static int head_hw(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, int groups, int stride, bool x_fm, hipStream_t st) {
+  if (s->head_from >= s->T) return UMB_OK;
+  const char* x = (const char*)ws->hw + (size_t)s->head_from * m->H * 2;
+  UmbGemmFused fh = {};
+  rms_from_ssq(fh, m, ws, groups, stride, s->head_from);
+  fh.pad1 = x_fm ? 1 : 0;
+  return lin(m->lm_head, x, m->H, ws->logits, s->T - s->head_from, m->dtype, st, /*EPI_ROUND*/1, &fh);
 }
 
 // ---- tensor parallelism: this rank holds 1/P of every linear (q/k/v, gate/up column-split; o, down
@@ -122,61 +187,11 @@ static inline int split_fm_tt(const UmbModel* m, const UmbWorkspace* ws, const U
 // Schedule 0 (default): one decoder layer = 8 launches; split-K partials are reduced at kernel boundaries by
 // small epilogue kernels.  Measured faster on MI355X than schedule 1: an in-kernel cross-workgroup hand-off costs
 // as much as a kernel boundary on the 8-XCD part (profiles/README.md), and it serialises a tail onto every GEMM.
-// fm: token tiles of the FM-ordered activations (split_fm_tt; 0 = row-major); more: another layer of THIS forward follows, i.e.
-// the normed residual this layer leaves is a GEMM operand (FM) and not the lm_head's / the next pipeline stage's input (row-major)
-// qn: Qwen3's per-head q / k norm weights of this layer (qk_eps their epsilon), applied by the q/k/v reduce; NULL: none
-static int layer_split(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbLayer& ly, int l,
-                       const void* next_norm, hipStream_t st, const UmbTP* tp = nullptr, int fm = 0, bool more = false,
-                       const UmbQwen3Norms* qn = nullptr, float qk_eps = 0.f) {
-  const int T = s->T, dt = m->dtype;
-  const size_t esz = 2;
-  char* kc = (char*)m->k_cache + (size_t)l * m->Hkv * m->Lmax * m->D * esz;
-  char* vt = (char*)m->vt_cache + (size_t)l * m->Hkv * VT_LD(m->Lmax) * m->D * esz;
-  UmbGemmFused fxm = {}, fgu = {};
-  fxm.pad1 = 1;                                             // x in FM order
-  fgu.pad1 = 3;                                             // x and the SiLU output in FM order
-  const UmbGemmFused* xf = fm ? &fxm : nullptr;
-  CK(lin(ly.qkv, ws->xn, m->H, ws->partial, T, dt, st, 0, xf));
-  if (qn)
-    CK(umb_reduce_qkv_rope_qknorm(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
-                                  m->rope_sin, ws->q, kc, vt, /*paired=*/1, ly.qkv_bias, nullptr, 0, 0, 0.f, 0.f, qn->q_norm,
-                                  qn->k_norm, qk_eps, dt, st));
-  else
-    CK(umb_reduce_qkv_rope(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
-                           m->rope_sin, ws->q, kc, vt, /*paired=*/1, ly.qkv_bias, dt, st));
-  CK(umb_tree_attn2(ws->attn, ws->q, kc, vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
-                    s->n_mask_keys, T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_chunk, ws->attn_splits, m->attn_scale,
-                    ws->attn_counters, fm, dt, st));
-  CK(lin(ly.o, ws->attn, m->Hq * m->D, ws->partial, T, dt, st, 0, xf, true));
-  int So = eff_s(ly.o, T, true);
-  if (tp_peer(tp, (long)T * m->H)) {
-    CK(umb_tp_publish(tp->peer, ws->partial, So, (int64_t)T * m->H, st));
-    CK(umb_tp_reduce_residual_norm(tp->peer, T, m->H, ws->h, ws->h, ws->xn, ly.norm2, m->eps, dt, st));
-  } else {
-    CK(tp_allreduce(tp, ws->partial, &So, (long)T * m->H, st));
-    CK(umb_reduce_residual_norm_fm(ws->partial, So, T, m->H, ws->h, ws->h, ws->xn, ly.norm2, m->eps, fm, dt, st));
-  }
-  if (ly.gu.S != 1) return UMB_EINVAL;     // gate/up rows are interleaved at load time: SiLU(gate)*up is the epilogue
-  CK(lin(ly.gu, ws->xn, m->H, ws->act, T, dt, st, /*EPI_SILU*/2, fm ? &fgu : nullptr));
-  CK(lin(ly.down, ws->act, m->I, ws->partial, T, dt, st, 0, xf, true));
-  int Sd = eff_s(ly.down, T, true);
-  if (tp_peer(tp, (long)T * m->H)) {
-    CK(umb_tp_publish(tp->peer, ws->partial, Sd, (int64_t)T * m->H, st));
-    CK(umb_tp_reduce_residual_norm(tp->peer, T, m->H, ws->h, ws->h, next_norm ? ws->xn : nullptr, next_norm, m->eps, dt, st));
-  } else {
-    CK(tp_allreduce(tp, ws->partial, &Sd, (long)T * m->H, st));
-    CK(umb_reduce_residual_norm_fm(ws->partial, Sd, T, m->H, ws->h, ws->h, next_norm ? ws->xn : nullptr, next_norm, m->eps,
-                                   more ? fm : 0, dt, st));
-  }
-  return UMB_OK;
-}
-
-// Schedule 0 with the RMSNorm deferred (ws->defer_norm; round 6): the same 8 launches, but the two residual reduces run N / 512
+//
+// With the RMSNorm deferred (ws->defer_norm; round 6): the same 8 launches, but the two residual reduces run N / 512
 // blocks per token row (umb_reduce_residual_hw: h, hw = h * w_next, sums of squares per block) instead of one block per row that
 // has to see the whole row before it can normalise -- at T = 13 thirteen CUs each pulled 128-256 KB of fp32 partials.  1 / rms is
-// applied where it commutes with the matmul: by the q/k/v reduce, by the gate/up epilogue, by the lm_head epilogue.  *groups:
-// how many sums of squares per token the producer of ws->hw left (H / 64 after the embedding kernel, H / 512
-// after a residual reduce).
+// applied where it commutes with the matmul: by the q/k/v reduce, by the gate/up epilogue, by the lm_head epilogue.
 // Forwards of <= 64 rows only: from 65 rows on the one-block-per-row reduce already fills the chip and the wide GEMMs do not
 // want a per-token factor in their epilogues (C3 / C4 iterations measured 1 % slower with it; the two regimes differ in their
 // int4 arithmetic anyway, so no invariance is lost across that boundary).
@@ -184,60 +199,63 @@ static inline bool use_defer(const UmbModel* m, const UmbWorkspace* ws, const Um
   return s->T <= 64 && ws->fused != 1 && ws->defer_norm && !tp_on(tp) && m->H % 512 == 0 && ws->ssq_stride >= m->H / 64 && ws->ssq_stride % 4 == 0 &&
          (m->H / 512) % 4 == 0;
 }
-static int prologue_defer(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const void* first_norm, int fm, int* groups,
-                          hipStream_t st) {
-  if (s->T < 1 || s->T > ws->Tmax) return UMB_EINVAL;
-  // one grouping of the sums of squares (per 64 columns) whatever the row count and the layout of hw: a token's 1 / rms is the
-  // same bits in a 1-row and in a 64-row forward
-  *groups = m->H / 64;
-  return umb_embed_prep_fm(ws->h, s->skip_embed ? nullptr : m->embed, m->H, s->T, s->tokens, s->positions, s->slots,
-                           s->prefix_len, s->tokens_all, s->n_ptr, s->tree_off, s->depth, ws->pos, ws->slot, ws->prefix,
-                           ws->hw, first_norm, ws->ssq, ws->ssq_stride, fm, m->dtype, st);
-}
-static int layer_split_defer(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbLayer& ly, int l,
-                             const void* next_norm, int* groups, hipStream_t st, int fm, bool more,
-                             const UmbQwen3Norms* qn = nullptr, float qk_eps = 0.f) {
+// groups: NULL = the norm is applied by the reduces (the GEMMs read the normed residual ws->xn); else the norm is deferred (they
+// read ws->hw) and *groups says how many sums of squares per token the producer of ws->hw left: H / 64 after the embedding
+// kernel, H / 512 after a residual reduce.
+// fm: token tiles of the FM-ordered activations (split_fm_tt; 0 = row-major); more: another layer of THIS forward follows, i.e.
+// the normed residual this layer leaves is a GEMM operand (FM) and not the lm_head's / the next pipeline stage's input (row-major)
+// qn: Qwen3's per-head q / k norm weights of this layer (qk_eps their epsilon), applied by the q/k/v reduce; NULL: none
+static int layer_split(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbLayer& ly, int l,
+                       const void* next_norm, int* groups, hipStream_t st, const UmbTP* tp, int fm, bool more,
+                       const UmbQwen3Norms* qn, float qk_eps) {
   const int T = s->T, dt = m->dtype;
-  const size_t esz = 2;
-  char* kc = (char*)m->k_cache + (size_t)l * m->Hkv * m->Lmax * m->D * esz;
-  char* vt = (char*)m->vt_cache + (size_t)l * m->Hkv * VT_LD(m->Lmax) * m->D * esz;
+  const KV kv = kv_slabs(m, l);
+  const bool df = groups != nullptr;
+  const void* x = df ? ws->hw : ws->xn;
   UmbGemmFused fxm = {}, fgu = {};
   fxm.pad1 = 1;                                             // x in FM order
   const UmbGemmFused* xf = fm ? &fxm : nullptr;
-  CK(lin(ly.qkv, ws->hw, m->H, ws->partial, T, dt, st, 0, xf));
+  CK(lin(ly.qkv, x, m->H, ws->partial, T, dt, st, 0, xf));
   if (qn)
     CK(umb_reduce_qkv_rope_qknorm(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
-                                  m->rope_sin, ws->q, kc, vt, /*paired=*/1, ly.qkv_bias, ws->ssq, *groups, ws->ssq_stride,
-                                  (float)m->H, m->eps, qn->q_norm, qn->k_norm, qk_eps, dt, st));
-  else
+                                  m->rope_sin, ws->q, kv.k, kv.vt, /*paired=*/1, ly.qkv_bias, df ? ws->ssq : nullptr,
+                                  df ? *groups : 0, df ? ws->ssq_stride : 0, df ? (float)m->H : 0.f, df ? m->eps : 0.f,
+                                  qn->q_norm, qn->k_norm, qk_eps, dt, st));
+  else if (df)
     CK(umb_reduce_qkv_rope2(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
-                            m->rope_sin, ws->q, kc, vt, /*paired=*/1, ly.qkv_bias, ws->ssq, *groups, ws->ssq_stride, (float)m->H,
-                            m->eps, dt, st));
-  CK(umb_tree_attn2(ws->attn, ws->q, kc, vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
-                    s->n_mask_keys, T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_chunk, ws->attn_splits, m->attn_scale,
-                    ws->attn_counters, fm, dt, st));
+                            m->rope_sin, ws->q, kv.k, kv.vt, /*paired=*/1, ly.qkv_bias, ws->ssq, *groups, ws->ssq_stride,
+                            (float)m->H, m->eps, dt, st));
+  else
+    CK(umb_reduce_qkv_rope(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
+                           m->rope_sin, ws->q, kv.k, kv.vt, /*paired=*/1, ly.qkv_bias, dt, st));
+  CK(tree_attn(m, ws, s, kv, fm, st));
+  // o and down end in the residual reduce, which leaves the next GEMM's operand (keep: there is one; not behind the last layer of
+  // an earlier pipeline stage): hw and its sums of squares where the norm is deferred, else xn -- under tensor parallelism once
+  // the ranks' partial sums have met
+  auto reduce = [&](const UmbLinear& li, const void* norm_w, bool keep, int out_fm) -> int {
+    int S = eff_s(li, T, true);
+    if (df)
+      return umb_reduce_residual_hw(ws->partial, S, T, m->H, ws->h, ws->h, keep ? ws->hw : nullptr, norm_w,
+                                    keep ? ws->ssq : nullptr, ws->ssq_stride, out_fm, dt, st);
+    if (tp_peer(tp, (long)T * m->H)) {
+      CK(umb_tp_publish(tp->peer, ws->partial, S, (int64_t)T * m->H, st));
+      return umb_tp_reduce_residual_norm(tp->peer, T, m->H, ws->h, ws->h, keep ? ws->xn : nullptr, norm_w, m->eps, dt, st);
+    }
+    CK(tp_allreduce(tp, ws->partial, &S, (long)T * m->H, st));
+    return umb_reduce_residual_norm_fm(ws->partial, S, T, m->H, ws->h, ws->h, keep ? ws->xn : nullptr, norm_w, m->eps, out_fm, dt,
+                                       st);
+  };
   CK(lin(ly.o, ws->attn, m->Hq * m->D, ws->partial, T, dt, st, 0, xf, true));
-  const int g2 = m->H / 512;
-  CK(umb_reduce_residual_hw(ws->partial, eff_s(ly.o, T, true), T, m->H, ws->h, ws->h, ws->hw, ly.norm2, ws->ssq, ws->ssq_stride, fm,
-                            dt, st));
+  CK(reduce(ly.o, ly.norm2, true, fm));
   if (ly.gu.S != 1) return UMB_EINVAL;     // gate/up rows are interleaved at load time: SiLU(gate)*up is the epilogue
-  fgu.ssq_in = ws->ssq; fgu.ssq_groups = g2; fgu.pad0 = ws->ssq_stride; fgu.ssq_dim = (float)m->H; fgu.eps = m->eps;
+  const int g2 = m->H / 512;
+  if (df) rms_from_ssq(fgu, m, ws, g2, ws->ssq_stride);
   fgu.pad1 = fm ? 3 : 0;                                    // x and the SiLU output in FM order
-  CK(lin(ly.gu, ws->hw, m->H, ws->act, T, dt, st, /*EPI_SILU*/2, &fgu));
+  CK(lin(ly.gu, x, m->H, ws->act, T, dt, st, /*EPI_SILU*/2, (df || fm) ? &fgu : nullptr));
   CK(lin(ly.down, ws->act, m->I, ws->partial, T, dt, st, 0, xf, true));
-  CK(umb_reduce_residual_hw(ws->partial, eff_s(ly.down, T, true), T, m->H, ws->h, ws->h, next_norm ? ws->hw : nullptr, next_norm,
-                            next_norm ? ws->ssq : nullptr, ws->ssq_stride, more ? fm : 0, dt, st));
-  *groups = g2;
+  CK(reduce(ly.down, next_norm, next_norm != nullptr, more ? fm : 0));
+  if (df) *groups = g2;
   return UMB_OK;
-}
-static int head_defer(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, int groups, hipStream_t st) {
-  if (s->head_from >= s->T) return UMB_OK;
-  const int rows = s->T - s->head_from;
-  const char* x = (const char*)ws->hw + (size_t)s->head_from * m->H * 2;
-  UmbGemmFused fh = {};
-  fh.ssq_in = ws->ssq + (size_t)s->head_from * ws->ssq_stride; fh.ssq_groups = groups; fh.pad0 = ws->ssq_stride;
-  fh.ssq_dim = (float)m->H; fh.eps = m->eps;
-  return lin(m->lm_head, x, m->H, ws->logits, rows, m->dtype, st, /*EPI_ROUND*/1, &fh);
 }
 
 // Schedule 1: one decoder layer = 5 launches.  RMSNorm is split: its weight is folded into the activations by
@@ -245,21 +263,17 @@ static int head_defer(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* 
 static int layer_fused(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbLayer& ly, int l,
                  const void* next_norm, hipStream_t st) {
   const int T = s->T, dt = m->dtype;
-  const size_t esz = 2;
-  char* kc = (char*)m->k_cache + (size_t)l * m->Hkv * m->Lmax * m->D * esz;
-  char* vt = (char*)m->vt_cache + (size_t)l * m->Hkv * VT_LD(m->Lmax) * m->D * esz;
+  const KV kv = kv_slabs(m, l);
   if (ly.qkv_bias) return UMB_EINVAL;          // projection bias: default schedule only
   UmbGemmFused fx = {};
   // 1. qkv GEMM -> (last split block) 1/rms, RoPE at tree positions, q out, K/V appended at their slots
-  fx.ssq_in = ws->ssq; fx.ssq_groups = ws->ssq_stride; fx.ssq_dim = (float)m->H; fx.eps = m->eps;
+  rms_from_ssq(fx, m, ws, ws->ssq_stride, 0);
   fx.counters = ws->counters;
   fx.pos = ws->pos; fx.slot = ws->slot; fx.cosT = m->rope_cos; fx.sinT = m->rope_sin;
-  fx.q_out = ws->q; fx.k_cache = kc; fx.vt_cache = vt; fx.Hq = m->Hq; fx.Hkv = m->Hkv; fx.D = m->D; fx.Lmax = m->Lmax;
+  fx.q_out = ws->q; fx.k_cache = kv.k; fx.vt_cache = kv.vt; fx.Hq = m->Hq; fx.Hkv = m->Hkv; fx.D = m->D; fx.Lmax = m->Lmax;
   CK(lin(ly.qkv, ws->hw, m->H, ws->partial, T, dt, st, /*EPI_QKV*/3, &fx));
   // 2. tree attention (+ fused split merge)
-  CK(umb_tree_attn(ws->attn, ws->q, kc, vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
-                   s->n_mask_keys, T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_chunk, ws->attn_splits, m->attn_scale,
-                   ws->attn_counters, dt, st));
+  CK(tree_attn(m, ws, s, kv, -1, st));
   // 3. o_proj GEMM -> h += o ; hw = h * norm2_w ; ssq
   UmbGemmFused fo = {};
   fo.counters = ws->counters; fo.h = ws->h; fo.hw = ws->hw; fo.norm_w = ly.norm2; fo.ssq_out = ws->ssq;
@@ -267,7 +281,7 @@ static int layer_fused(const UmbModel* m, const UmbWorkspace* ws, const UmbStep*
   CK(lin(ly.o, ws->attn, m->Hq * m->D, ws->partial, T, dt, st, /*EPI_RESID*/4, &fo));
   // 4. gate/up GEMM (unsplit, interleaved rows) -> act = SiLU(gate/rms) * up/rms
   UmbGemmFused fg = {};
-  fg.ssq_in = ws->ssq; fg.ssq_groups = ws->ssq_stride; fg.ssq_dim = (float)m->H; fg.eps = m->eps;
+  rms_from_ssq(fg, m, ws, ws->ssq_stride, 0);
   if (ly.gu.S != 1) return UMB_EINVAL;
   CK(lin(ly.gu, ws->hw, m->H, ws->act, T, dt, st, /*EPI_SILU*/2, &fg));
   // 5. down GEMM -> h += d ; hw = h * (next layer's norm1 | final norm) ; ssq
@@ -318,21 +332,13 @@ static inline bool qkv_on_split_kernel(const UmbLinear& l) {
   return l.S > 1 && blocks > 256 && blocks < 512;
 }
 
-static int prologue_ll(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const void* first_norm, hipStream_t st) {
-  if (s->T < 1 || s->T > ws->Tmax) return UMB_EINVAL;
-  return umb_embed_ll(ws->h, s->skip_embed ? nullptr : m->embed, m->H, m->V, m->Lmax, s->T, s->tokens, s->positions,
-                      s->slots, s->prefix_len, s->tokens_all, s->n_ptr, s->tree_off, s->depth, ws->pos, ws->slot,
-                      ws->prefix, ws->hw, first_norm, ws->ssq, ws->ssq_stride, m->dtype, st);
-}
 
 // ssq_groups: how many partial sums of squares the producer of ws->hw left per token (4 after the embedding kernel,
 // N / 16 / R after a residual GEMM)
 static int layer_ll(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbLayer& ly, int l,
                     const void* next_norm, int* ssq_groups, hipStream_t st) {
   const int T = s->T, dt = m->dtype;
-  const size_t esz = 2;
-  char* kc = (char*)m->k_cache + (size_t)l * m->Hkv * m->Lmax * m->D * esz;
-  char* vt = (char*)m->vt_cache + (size_t)l * m->Hkv * VT_LD(m->Lmax) * m->D * esz;
+  const KV kv = kv_slabs(m, l);
   const int og = ll_groups(ly.o), dg = ll_groups(ly.down);
   if (og > ws->ssq_stride || dg > ws->ssq_stride) return UMB_EINVAL;
   // 1. qkv: 1/rms, (+bias), RoPE at the tree positions, q out, K / V appended at their slots.  A linear whose row groups
@@ -343,39 +349,36 @@ static int layer_ll(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s,
     fs.pad1 = 1;                                            // x in FM layout
     CK(lin(ly.qkv, ws->hw, m->H, ws->partial, T, dt, st, 0, &fs));
     CK(umb_reduce_qkv_rope2(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
-                            m->rope_sin, ws->q, kc, vt, /*paired=*/1, ly.qkv_bias, ws->ssq, *ssq_groups, ws->ssq_stride,
+                            m->rope_sin, ws->q, kv.k, kv.vt, /*paired=*/1, ly.qkv_bias, ws->ssq, *ssq_groups, ws->ssq_stride,
                             (float)m->H, m->eps, dt, st));
   } else {
-  UmbGemmLL fq = {};
-  fq.ssq_in = ws->ssq; fq.ssq_groups = *ssq_groups; fq.ssq_in_stride = ws->ssq_stride; fq.ssq_dim = (float)m->H; fq.eps = m->eps;
-  fq.pos = ws->pos; fq.slot = ws->slot; fq.cosT = m->rope_cos; fq.sinT = m->rope_sin; fq.q_out = ws->q; fq.k_cache = kc;
-  fq.vt_cache = vt; fq.bias = ly.qkv_bias; fq.Hq = m->Hq; fq.Hkv = m->Hkv; fq.D = m->D; fq.Lmax = m->Lmax;
-  CK(umb_gemm_ll(nullptr, ws->hw, ly.qkv.w, ly.qkv.meta, T, ly.qkv.N, ly.qkv.K, ly.qkv.awq, 3, &fq, dt, st));
+    UmbGemmLL fq = {};
+    rms_from_ssq(fq, m, ws, *ssq_groups);
+    qkv_epilogue(fq, m, ws, kv, ly.qkv_bias);
+    CK(umb_gemm_ll(nullptr, ws->hw, ly.qkv.w, ly.qkv.meta, T, ly.qkv.N, ly.qkv.K, ly.qkv.awq, 3, &fq, dt, st));
   }
   // 2. tree attention, output in FM layout for the o-projection
-  CK(umb_tree_attn2(ws->attn, ws->q, kc, vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
-                    s->n_mask_keys, T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_chunk, ws->attn_splits, m->attn_scale,
-                    ws->attn_counters, umb_ll_token_tiles(T), dt, st));
+  CK(tree_attn(m, ws, s, kv, umb_ll_token_tiles(T), st));
   // 3. o_proj: h += o ; hw = h * norm2_w ; sums of squares
   UmbGemmLL fo = {};
-  fo.h = ws->h; fo.hw = ws->hw; fo.norm_w = ly.norm2; fo.ssq_out = ws->ssq; fo.ssq_out_stride = ws->ssq_stride;
+  resid_epilogue(fo, ws, ly.norm2);
   CK(umb_gemm_ll(nullptr, ws->attn, ly.o.w, ly.o.meta, T, ly.o.N, ly.o.K, ly.o.awq, 4, &fo, dt, st));
   // 4. gate/up (rows interleaved at load): act = SiLU(gate / rms) * up / rms, FM layout.  A linear with enough n-tiles
   // to fill the chip without any K split runs on the LDS-shared kernel of gemm.hip (4 waves share each activation
   // fragment; 70B gate/up: 53 vs 65 us), reading and writing the same FM buffers.
   if (gu_on_shared_kernel(ly.gu) && og % 4 == 0 && ws->ssq_stride % 4 == 0) {
     UmbGemmFused fs = {};
-    fs.ssq_in = ws->ssq; fs.ssq_groups = og; fs.pad0 = ws->ssq_stride; fs.ssq_dim = (float)m->H; fs.eps = m->eps;
+    rms_from_ssq(fs, m, ws, og, ws->ssq_stride);
     fs.pad1 = 3;                                            // x and the SiLU output in FM layout
     CK(lin(ly.gu, ws->hw, m->H, ws->act, T, dt, st, /*EPI_SILU*/2, &fs));
   } else {
     UmbGemmLL fg = {};
-    fg.ssq_in = ws->ssq; fg.ssq_groups = og; fg.ssq_in_stride = ws->ssq_stride; fg.ssq_dim = (float)m->H; fg.eps = m->eps;
+    rms_from_ssq(fg, m, ws, og);
     CK(umb_gemm_ll(ws->act, ws->hw, ly.gu.w, ly.gu.meta, T, ly.gu.N, ly.gu.K, ly.gu.awq, 2, &fg, dt, st));
   }
   // 5. down: h += d ; hw = h * (next layer's norm1 | final norm) ; sums of squares
   UmbGemmLL fd = {};
-  fd.h = ws->h; fd.hw = ws->hw; fd.norm_w = next_norm; fd.ssq_out = ws->ssq; fd.ssq_out_stride = ws->ssq_stride;
+  resid_epilogue(fd, ws, next_norm);
   CK(umb_gemm_ll(nullptr, ws->act, ly.down.w, ly.down.meta, T, ly.down.N, ly.down.K, ly.down.awq, 4, &fd, dt, st));
   *ssq_groups = dg;
   return UMB_OK;
@@ -393,15 +396,11 @@ static int head_ll(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, 
     return umb_head_stream(ws->logits, ws->hw, ws->ssq, ws->ssq_stride, ssq_groups, m->eps, m->lm_head.w_rows, s->T, m->lm_head.N,
                            m->H, umb_ll_token_tiles(s->T), m->dtype, st);
   if (!(env && env[0] == 'l') && s->head_from == 0 && m->lm_head.S == 1 && !m->lm_head.awq && ssq_groups % 4 == 0 &&
-      ws->ssq_stride % 4 == 0) {
-    UmbGemmFused fs = {};
-    fs.ssq_in = ws->ssq; fs.ssq_groups = ssq_groups; fs.pad0 = ws->ssq_stride; fs.ssq_dim = (float)m->H; fs.eps = m->eps;
-    fs.pad1 = 1;                                            // x in FM layout
-    return lin(m->lm_head, ws->hw, m->H, ws->logits, s->T, m->dtype, st, /*EPI_ROUND*/1, &fs);
-  }
+      ws->ssq_stride % 4 == 0)
+    return head_hw(m, ws, s, ssq_groups, ws->ssq_stride, /*x_fm=*/true, st);
   UmbGemmLL fh = {};
   fh.row_from = s->head_from; fh.round_out = 1;
-  fh.ssq_in = ws->ssq; fh.ssq_groups = ssq_groups; fh.ssq_in_stride = ws->ssq_stride; fh.ssq_dim = (float)m->H; fh.eps = m->eps;
+  rms_from_ssq(fh, m, ws, ssq_groups);
   return umb_gemm_ll(ws->logits, ws->hw, m->lm_head.w, m->lm_head.meta, s->T, m->lm_head.N, m->lm_head.K, m->lm_head.awq,
                      0, &fh, m->dtype, st);
 }
@@ -422,40 +421,37 @@ static inline bool use_gv(const UmbModel* m, const UmbWorkspace* ws, const UmbSt
   const int og = umb_gemv_groups(s->T, ly.o.N, ly.o.K), dg = umb_gemv_groups(s->T, ly.down.N, ly.down.K);
   return og <= ws->ssq_stride && dg <= ws->ssq_stride && og % 4 == 0 && dg % 4 == 0 && (m->H / 64) % 4 == 0;
 }
-static int prologue_gv(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const void* first_norm, int* groups,
-                       hipStream_t st) {
-  if (s->T < 1 || s->T > ws->Tmax) return UMB_EINVAL;
-  *groups = m->H / 64;                         // umb_embed_prep: one sum of squares per 64 columns
-  return umb_embed_prep(ws->h, s->skip_embed ? nullptr : m->embed, m->H, s->T, s->tokens, s->positions, s->slots,
-                        s->prefix_len, s->tokens_all, s->n_ptr, s->tree_off, s->depth, ws->pos, ws->slot, ws->prefix,
-                        ws->hw, first_norm, ws->ssq, ws->ssq_stride, m->dtype, st);
-}
+// groups: as ssq_groups of layer_ll (H / 64 after umb_embed_prep: one sum of squares per 64 columns)
 static int layer_gv(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbLayer& ly, int l,
                     const void* next_norm, int* groups, hipStream_t st) {
   const int T = s->T, dt = m->dtype;
-  const size_t esz = 2;
-  char* kc = (char*)m->k_cache + (size_t)l * m->Hkv * m->Lmax * m->D * esz;
-  char* vt = (char*)m->vt_cache + (size_t)l * m->Hkv * VT_LD(m->Lmax) * m->D * esz;
+  const KV kv = kv_slabs(m, l);
   UmbGemmLL fq = {};
-  fq.ssq_in = ws->ssq; fq.ssq_groups = *groups; fq.ssq_in_stride = ws->ssq_stride; fq.ssq_dim = (float)m->H; fq.eps = m->eps;
-  fq.pos = ws->pos; fq.slot = ws->slot; fq.cosT = m->rope_cos; fq.sinT = m->rope_sin; fq.q_out = ws->q; fq.k_cache = kc;
-  fq.vt_cache = vt; fq.bias = ly.qkv_bias; fq.Hq = m->Hq; fq.Hkv = m->Hkv; fq.D = m->D; fq.Lmax = m->Lmax;
+  rms_from_ssq(fq, m, ws, *groups);
+  qkv_epilogue(fq, m, ws, kv, ly.qkv_bias);
   CK(umb_gemv(nullptr, ws->hw, ly.qkv.w_rows, T, ly.qkv.N, ly.qkv.K, 3, &fq, dt, st));
-  CK(umb_tree_attn(ws->attn, ws->q, kc, vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
-                   s->n_mask_keys, T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_chunk, ws->attn_splits, m->attn_scale,
-                   ws->attn_counters, dt, st));
+  CK(tree_attn(m, ws, s, kv, -1, st));
   UmbGemmLL fo = {};
-  fo.h = ws->h; fo.hw = ws->hw; fo.norm_w = ly.norm2; fo.ssq_out = ws->ssq; fo.ssq_out_stride = ws->ssq_stride;
+  resid_epilogue(fo, ws, ly.norm2);
   CK(umb_gemv(nullptr, ws->attn, ly.o.w_rows, T, ly.o.N, ly.o.K, 4, &fo, dt, st));
   UmbGemmLL fg = {};
-  fg.ssq_in = ws->ssq; fg.ssq_groups = umb_gemv_groups(T, ly.o.N, ly.o.K); fg.ssq_in_stride = ws->ssq_stride;
-  fg.ssq_dim = (float)m->H; fg.eps = m->eps;
+  rms_from_ssq(fg, m, ws, umb_gemv_groups(T, ly.o.N, ly.o.K));
   CK(umb_gemv(ws->act, ws->hw, ly.gu.w_rows, T, ly.gu.N, ly.gu.K, 2, &fg, dt, st));
   UmbGemmLL fd = {};
-  fd.h = ws->h; fd.hw = ws->hw; fd.norm_w = next_norm; fd.ssq_out = ws->ssq; fd.ssq_out_stride = ws->ssq_stride;
+  resid_epilogue(fd, ws, next_norm);
   CK(umb_gemv(nullptr, ws->act, ly.down.w_rows, T, ly.down.N, ly.down.K, 4, &fd, dt, st));
   *groups = umb_gemv_groups(T, ly.down.N, ly.down.K);
   return UMB_OK;
+}
+static int head_gv(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, int groups, hipStream_t st) {
+  if (s->head_from >= s->T) return UMB_OK;
+  const int rows = s->T - s->head_from;
+  const char* x = (const char*)ws->hw + (size_t)s->head_from * m->H * 2;
+  // the head's rows as a plain row-major table (a tied model's embedding table): the streaming engine of chain.hip
+  if (m->lm_head.w_rows && umb_head_stream_ok(rows, m->lm_head.N, m->H))
+    return umb_head_stream(ws->logits, x, ws->ssq + (size_t)s->head_from * ws->ssq_stride, ws->ssq_stride, groups, m->eps,
+                           m->lm_head.w_rows, rows, m->lm_head.N, m->H, 0, m->dtype, st);
+  return head_hw(m, ws, s, groups, ws->ssq_stride, /*x_fm=*/false, st);
 }
 // ---- persistent chain (chain.hip): the GEMV schedule's layer as tree attention + ONE launch (o, gate/up, down, next q/k/v)
 static inline bool use_chain(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s) {
@@ -478,8 +474,8 @@ static int chain_launch(const UmbModel* m, const UmbWorkspace* ws, const UmbStep
   if (lt >= 0) {
     const UmbLayer& ly = m->layers[lt];
     c.tail = 1; c.w_qkv = ly.qkv.w_rows;
-    c.k_cache = (char*)m->k_cache + (size_t)lt * m->Hkv * m->Lmax * m->D * 2;
-    c.vt_cache = (char*)m->vt_cache + (size_t)lt * m->Hkv * VT_LD(m->Lmax) * m->D * 2;
+    const KV kv = kv_slabs(m, lt);
+    c.k_cache = kv.k; c.vt_cache = kv.vt;
     c.pos = ws->pos; c.slot = ws->slot; c.cosT = m->rope_cos; c.sinT = m->rope_sin; c.q_out = ws->q;
   }
   c.NQKV = m->layers[lt >= 0 ? lt : lf].qkv.N;
@@ -489,107 +485,85 @@ static int chain_launch(const UmbModel* m, const UmbWorkspace* ws, const UmbStep
   c.Hq = m->Hq; c.Hkv = m->Hkv; c.D = m->D; c.Lmax = m->Lmax; c.eps = m->eps;
   return umb_draft_chain(&c, m->dtype, st);
 }
-static int attn_gv(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, int l, hipStream_t st) {
-  char* kc = (char*)m->k_cache + (size_t)l * m->Hkv * m->Lmax * m->D * 2;
-  char* vt = (char*)m->vt_cache + (size_t)l * m->Hkv * VT_LD(m->Lmax) * m->D * 2;
-  return umb_tree_attn(ws->attn, ws->q, kc, vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
-                       s->n_mask_keys, s->T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_chunk, ws->attn_splits, m->attn_scale,
-                       ws->attn_counters, m->dtype, st);
-}
-static int head_gv(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, int groups, hipStream_t st) {
-  if (s->head_from >= s->T) return UMB_OK;
-  const int rows = s->T - s->head_from;
-  const char* x = (const char*)ws->hw + (size_t)s->head_from * m->H * 2;
-  // the head's rows as a plain row-major table (a tied model's embedding table): the streaming engine of chain.hip
-  if (m->lm_head.w_rows && umb_head_stream_ok(rows, m->lm_head.N, m->H))
-    return umb_head_stream(ws->logits, x, ws->ssq + (size_t)s->head_from * ws->ssq_stride, ws->ssq_stride, groups, m->eps,
-                           m->lm_head.w_rows, rows, m->lm_head.N, m->H, 0, m->dtype, st);
-  UmbGemmFused fh = {};
-  fh.ssq_in = ws->ssq + (size_t)s->head_from * ws->ssq_stride; fh.ssq_groups = groups; fh.pad0 = ws->ssq_stride;
-  fh.ssq_dim = (float)m->H; fh.eps = m->eps;
-  return lin(m->lm_head, x, m->H, ws->logits, rows, m->dtype, st, /*EPI_ROUND*/1, &fh);
-}
-
-static int layer(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbLayer& ly, int l,
-                 const void* next_norm, hipStream_t st, int fm = 0, bool more = false) {
-  return ws->fused == 1 ? layer_fused(m, ws, s, ly, l, next_norm, st) : layer_split(m, ws, s, ly, l, next_norm, st, nullptr, fm, more);
-}
-
-static int head(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, hipStream_t st) {
-  if (s->head_from >= s->T) return UMB_OK;
-  const int rows = s->T - s->head_from;
-  if (ws->fused != 1) {
-    const char* xn = (const char*)ws->xn + (size_t)s->head_from * m->H * 2;
-    return lin(m->lm_head, xn, m->H, ws->logits, rows, m->dtype, st, /*EPI_ROUND*/1, nullptr);
-  }
-  const char* x = (const char*)ws->hw + (size_t)s->head_from * m->H * 2;
-  UmbGemmFused fh = {};
-  fh.ssq_in = ws->ssq + (size_t)s->head_from * ws->ssq_stride; fh.ssq_groups = ws->ssq_stride;
-  fh.ssq_dim = (float)m->H; fh.eps = m->eps;
-  return lin(m->lm_head, x, m->H, ws->logits, rows, m->dtype, st, /*EPI_ROUND*/1, &fh);
-}
-
-static int model_forward(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbTP* tp, hipStream_t st) {
+// the chain's layers and head, behind the GEMV prologue.  2 launches per layer: the first q/k/v alone, then per layer tree
+// attention + the chain into the next q/k/v
+static int chain_forward(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, int groups, hipStream_t st) {
   const int lb = s->layer_begin, le = s->layer_end;
-  if (lb < 0 || le > m->L || lb >= le) return UMB_EINVAL;
-  if (fp8_refused(m, ws, s) || (tp_on(tp) && fp8_layers(m, s))) return UMB_EINVAL;
-  if (tp_on(tp)) {
-    // row-split partial sums meet between the GEMM and its reduce kernel: the 8-launch schedule only
-    if (ws->fused != 0) return UMB_EINVAL;
-    CK(prologue(m, ws, s, m->layers[lb].norm1, st));
-    for (int l = lb; l < le; ++l) {
-      const void* nn = (l + 1 < le) ? m->layers[l + 1].norm1 : (le == m->L ? m->final_norm : nullptr);
-      CK(layer_split(m, ws, s, m->layers[l], l, nn, st, tp));
-    }
-    if (le == m->L) CK(head(m, ws, s, st));
-    return UMB_OK;
-  }
-  if (use_gv(m, ws, s)) {
-    int groups = 0;
-    CK(prologue_gv(m, ws, s, m->layers[lb].norm1, &groups, st));
-    if (use_chain(m, ws, s)) {
-      // 2 launches per layer: the first q/k/v alone, then per layer tree attention + the chain into the next q/k/v
-      CK(chain_launch(m, ws, s, -1, lb, nullptr, groups, st));
-      for (int l = lb; l < le; ++l) {
-        const void* nn = (l + 1 < le) ? m->layers[l + 1].norm1 : (le == m->L ? m->final_norm : nullptr);
-        CK(attn_gv(m, ws, s, l, st));
-        CK(chain_launch(m, ws, s, l, l + 1 < le ? l + 1 : -1, nn, 0, st));
-      }
-      groups = umb_gemv_groups(s->T, m->layers[lb].down.N, m->layers[lb].down.K);
-      if (le == m->L) CK(head_gv(m, ws, s, groups, st));
-      return UMB_OK;
-    }
-    for (int l = lb; l < le; ++l) {
-      const void* nn = (l + 1 < le) ? m->layers[l + 1].norm1 : (le == m->L ? m->final_norm : nullptr);
-      CK(layer_gv(m, ws, s, m->layers[l], l, nn, &groups, st));
-    }
-    if (le == m->L) CK(head_gv(m, ws, s, groups, st));
-    return UMB_OK;
-  }
-  const bool ll = use_ll(m, ws, s);
-  const int fm = ll ? 0 : split_fm_tt(m, ws, s, nullptr);
-  const bool df = !ll && use_defer(m, ws, s, nullptr);
-  int sg = 4;
-  CK(ll ? prologue_ll(m, ws, s, m->layers[lb].norm1, st)
-        : df ? prologue_defer(m, ws, s, m->layers[lb].norm1, fm, &sg, st) : prologue(m, ws, s, m->layers[lb].norm1, st, fm));
+  CK(chain_launch(m, ws, s, -1, lb, nullptr, groups, st));
   for (int l = lb; l < le; ++l) {
-    const void* nn = (l + 1 < le) ? m->layers[l + 1].norm1 : (le == m->L ? m->final_norm : nullptr);
-    CK(ll ? layer_ll(m, ws, s, m->layers[l], l, nn, &sg, st)
-          : df ? layer_split_defer(m, ws, s, m->layers[l], l, nn, &sg, st, fm, l + 1 < le)
-               : layer(m, ws, s, m->layers[l], l, nn, st, fm, l + 1 < le));
+    CK(tree_attn(m, ws, s, kv_slabs(m, l), -1, st));
+    CK(chain_launch(m, ws, s, l, l + 1 < le ? l + 1 : -1, next_norm_of(m, l, le), 0, st));
   }
-  if (le == m->L) CK(ll ? head_ll(m, ws, s, sg, st) : df ? head_defer(m, ws, s, sg, st) : head(m, ws, s, st));
+  groups = umb_gemv_groups(s->T, m->layers[lb].down.N, m->layers[lb].down.K);
+  if (le == m->L) CK(head_gv(m, ws, s, groups, st));
   return UMB_OK;
 }
 
-extern "C" int umb_model_forward(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, hipStream_t st) {
-  return model_forward(m, ws, s, nullptr, st);
-}
+// ---- the schedule of one forward: chosen once (choose), then asked for the prologue, each layer and the head
+struct Sched {
+  const UmbModel* m; const UmbWorkspace* ws; const UmbStep* s; hipStream_t st;
+  enum Kind { SPLIT, DEFER, FUSED, LL, GV } kind;
+  int fm;                          // SPLIT / DEFER: token tiles of the FM-ordered activations (split_fm_tt)
+  int groups;                      // DEFER / LL / GV: sums of squares per token the last producer of ws->hw left
+  const UmbTP* tp;                 // SPLIT: tensor parallelism, or NULL
+  const UmbQwen3* q3;              // SPLIT / DEFER: Qwen3's per-head norms, or NULL
 
-extern "C" int umb_model_forward_tp(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbTP* tp,
-                                    hipStream_t st) {
-  if (tp && (tp->world < 1 || tp->rank < 0 || tp->rank >= tp->world)) return UMB_EINVAL;
-  return model_forward(m, ws, s, tp, st);
+  // embedding (stage 0) / index resolution + the first layer's operand: xn, or hw and the sums of squares of h
+  int pro() {
+    const void* first_norm = m->layers[s->layer_begin].norm1;
+    switch (kind) {
+      case SPLIT:
+        CK(embed(m, ws, s, nullptr, nullptr, nullptr, -1, st));
+        return umb_rmsnorm_fm(ws->xn, ws->h, first_norm, m->eps, s->T, m->H, fm, m->dtype, st);
+      case DEFER:
+        // one grouping of the sums of squares (per 64 columns) whatever the row count and the layout of hw: a token's 1 / rms is
+        // the same bits in a 1-row and in a 64-row forward
+        groups = m->H / 64;
+        return embed(m, ws, s, ws->hw, first_norm, ws->ssq, fm, st);
+      case GV: groups = m->H / 64; [[fallthrough]];       // umb_embed_prep: one sum of squares per 64 columns
+      case FUSED: return embed(m, ws, s, ws->hw, first_norm, ws->ssq, -1, st);
+      case LL: break;
+    }
+    if (!rows_ok(ws, s)) return UMB_EINVAL;
+    groups = 4;
+    return umb_embed_ll(ws->h, s->skip_embed ? nullptr : m->embed, m->H, m->V, m->Lmax, s->T, s->tokens, s->positions,
+                        s->slots, s->prefix_len, s->tokens_all, s->n_ptr, s->tree_off, s->depth, ws->pos, ws->slot,
+                        ws->prefix, ws->hw, first_norm, ws->ssq, ws->ssq_stride, m->dtype, st);
+  }
+  // ly: layer l, rebased into its device slab where it is streamed
+  int lay(const UmbLayer& ly, int l, const void* next_norm) {
+    switch (kind) {
+      case FUSED: return layer_fused(m, ws, s, ly, l, next_norm, st);
+      case LL: return layer_ll(m, ws, s, ly, l, next_norm, &groups, st);
+      case GV: return layer_gv(m, ws, s, ly, l, next_norm, &groups, st);
+      default:
+        return layer_split(m, ws, s, ly, l, next_norm, kind == DEFER ? &groups : nullptr, st, tp, fm, l + 1 < s->layer_end,
+                           q3 ? &q3->norms[l] : nullptr, q3 ? q3->qk_eps : 0.f);
+    }
+  }
+  int hd() {
+    switch (kind) {
+      case DEFER: return head_hw(m, ws, s, groups, ws->ssq_stride, false, st);
+      case FUSED: return head_hw(m, ws, s, ws->ssq_stride, 0, false, st);
+      case LL: return head_ll(m, ws, s, groups, st);
+      case GV: return head_gv(m, ws, s, groups, st);
+      default: return head_xn(m, ws, s, st);
+    }
+  }
+};
+// The precedence of the schedules: GEMV (where the caller allows it: resident forwards) before low latency before the split
+// family, whose deferred form wins where use_defer allows it.  A tensor-parallel forward arrives with ws->fused == 0, which
+// use_gv and use_ll refuse, and split_fm_tt / use_defer refuse tp themselves.
+static Sched choose(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbTP* tp, bool gemv, const UmbQwen3* q3,
+                    hipStream_t st) {
+  Sched sc = {m, ws, s, st, Sched::SPLIT, 0, 0, tp, q3};
+  if (gemv && use_gv(m, ws, s)) sc.kind = Sched::GV;
+  else if (use_ll(m, ws, s)) sc.kind = Sched::LL;
+  else {
+    sc.fm = split_fm_tt(m, ws, s, tp);
+    sc.kind = use_defer(m, ws, s, tp) ? Sched::DEFER : ws->fused == 1 ? Sched::FUSED : Sched::SPLIT;
+  }
+  return sc;
 }
 
 // ---- offload: double-buffered layer streaming, event ordered (no device-wide syncs)
@@ -606,12 +580,19 @@ static UmbLayer rebase(const UmbLayer& in, const void* base) {
   return o;
 }
 
-// pro(): embedding / prologue; lay(layer, l, next_norm): one decoder layer on the (possibly rebased) layer; hd(): lm_head
-template <class Pro, class Lay, class Head>
-static int offload_forward(const UmbModel* m, const UmbStep* s, const UmbOffload* off, hipStream_t st, Pro&& pro, Lay&& lay,
-                           Head&& hd) {
+
+// The one layer loop over a schedule sc.  sc.pro(): embedding / prologue; sc.lay(layer, l, next_norm): one decoder layer on the
+// (possibly rebased) layer; sc.hd(): lm_head.  off == NULL: every layer is resident.  pro_done: the caller has run the prologue.
+template <class Sch>
+static int forward_loop(const UmbModel* m, const UmbStep* s, const UmbOffload* off, hipStream_t st, Sch& sc, bool pro_done = false) {
   const int lb = s->layer_begin, le = s->layer_end;
-  if (lb < 0 || le > m->L || lb >= le) return UMB_EINVAL;
+  if (!off) {
+    if (!pro_done) CK(sc.pro());
+    for (int l = lb; l < le; ++l) CK(sc.lay(m->layers[l], l, next_norm_of(m, l, le)));
+    if (le == m->L) CK(sc.hd());
+    return UMB_OK;
+  }
+  if (!range_ok(m, s)) return UMB_EINVAL;
   const int NS = off->n_slabs;
   if (NS < 2 || NS > UMB_MAX_SLABS) return UMB_EINVAL;
   hipStream_t cs = (hipStream_t)off->copy_stream;
@@ -650,7 +631,7 @@ static int offload_forward(const UmbModel* m, const UmbStep* s, const UmbOffload
   }
   if (pf) for (int i = 0; i < UMB_MAX_SLABS; ++i) pf[i] = -1;
 
-  CK(pro());
+  CK(sc.pro());
   for (int l = lb; l < le; ++l) {
     UmbLayer cur = m->layers[l];
     int buf = -1;
@@ -659,8 +640,7 @@ static int offload_forward(const UmbModel* m, const UmbStep* s, const UmbOffload
       if (hipStreamWaitEvent(st, (hipEvent_t)off->ev_copied[buf], 0) != hipSuccess) return UMB_EHIP;
       cur = rebase(m->layers[l], off->dev_slab[buf]);
     }
-    const void* nn = (l + 1 < le) ? m->layers[l + 1].norm1 : (le == m->L ? m->final_norm : nullptr);
-    CK(lay(cur, l, nn));
+    CK(sc.lay(cur, l, next_norm_of(m, l, le)));
     if (buf >= 0) {
       ++used;
       if (hipEventRecord((hipEvent_t)off->ev_free[buf], st) != hipSuccess) return UMB_EHIP;
@@ -682,130 +662,113 @@ static int offload_forward(const UmbModel* m, const UmbStep* s, const UmbOffload
       for (int i = 0; i < nfirst; ++i) CK(issue_copy(first[i], i));
     for (int i = 0; i < NS; ++i) pf[i] = first[i];
   }
-  if (le == m->L) CK(hd());
+  if (le == m->L) CK(sc.hd());
   return UMB_OK;
+}
+
+// Llama (and Qwen2: q/k/v bias) forwards: validate, choose, run.  q3: the Qwen3 entry points come through here too.
+static int llama_forward(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbTP* tp, const UmbOffload* off,
+                         const UmbQwen3* q3, hipStream_t st) {
+  if (!range_ok(m, s) || fp8_refused(m, ws, s, /*plain=*/!tp_on(tp) && !off)) return UMB_EINVAL;
+  // tensor parallel: row-split partial sums meet between the GEMM and its reduce kernel: the 8-launch schedule only
+  if (tp_on(tp) && ws->fused != 0) return UMB_EINVAL;
+  // a streamed forward never takes GEMV or the chain: their row-major copies are resident layers' only
+  Sched sc = choose(m, ws, s, tp, /*gemv=*/!off, q3, st);
+  if (sc.kind != Sched::GV) return forward_loop(m, s, off, st, sc);
+  // the chain is asked for behind the prologue, and has a loop of its own shape
+  CK(sc.pro());
+  if (use_chain(m, ws, s)) return chain_forward(m, ws, s, sc.groups, st);
+  return forward_loop(m, s, off, st, sc, /*pro_done=*/true);
+}
+
+extern "C" int umb_model_forward(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, hipStream_t st) {
+  return llama_forward(m, ws, s, nullptr, nullptr, nullptr, st);
+}
+
+extern "C" int umb_model_forward_tp(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbTP* tp,
+                                    hipStream_t st) {
+  if (tp && (tp->world < 1 || tp->rank < 0 || tp->rank >= tp->world)) return UMB_EINVAL;
+  return llama_forward(m, ws, s, tp, nullptr, nullptr, st);
 }
 
 extern "C" int umb_model_forward_offload(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s,
                                          const UmbOffload* off, hipStream_t st) {
-  const int lb = s->layer_begin, le = s->layer_end;
-  if (lb < 0 || le > m->L || lb >= le) return UMB_EINVAL;
-  if (m->lm_head.awq == 2 || fp8_layers(m, s)) return UMB_EINVAL;      // FP8 linears: resident forwards only
-  const bool ll = use_ll(m, ws, s);
-  const int fm = ll ? 0 : split_fm_tt(m, ws, s, nullptr);
-  const bool df = !ll && use_defer(m, ws, s, nullptr);
-  int sg = 4;
-  return offload_forward(
-      m, s, off, st,
-      [&]() {
-        return ll ? prologue_ll(m, ws, s, m->layers[lb].norm1, st)
-                  : df ? prologue_defer(m, ws, s, m->layers[lb].norm1, fm, &sg, st) : prologue(m, ws, s, m->layers[lb].norm1, st, fm);
-      },
-      [&](const UmbLayer& cur, int l, const void* nn) {
-        return ll ? layer_ll(m, ws, s, cur, l, nn, &sg, st)
-                  : df ? layer_split_defer(m, ws, s, cur, l, nn, &sg, st, fm, l + 1 < le) : layer(m, ws, s, cur, l, nn, st, fm, l + 1 < le);
-      },
-      [&]() { return ll ? head_ll(m, ws, s, sg, st) : df ? head_defer(m, ws, s, sg, st) : head(m, ws, s, st); });
+  return llama_forward(m, ws, s, nullptr, off, nullptr, st);
 }
 
 // ---- Gemma-2 (umbrella/models/gemma.py, gemma_layer.py): schedule 0 with Gemma's arithmetic, row-major activations.
-// prologue: embedding gather, h <- round(h * round(sqrt H)), xn <- gemma_norm(h, input_layernorm)
-static int prologue_gemma2(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbGemma2* g, hipStream_t st) {
-  if (s->T < 1 || s->T > ws->Tmax) return UMB_EINVAL;
-  CK(umb_embed_prep(ws->h, s->skip_embed ? nullptr : m->embed, m->H, s->T, s->tokens, s->positions, s->slots,
-                    s->prefix_len, s->tokens_all, s->n_ptr, s->tree_off, s->depth, ws->pos, ws->slot, ws->prefix,
-                    nullptr, nullptr, nullptr, 0, m->dtype, st));
-  return umb_gemma_rmsnorm(ws->xn, ws->h, m->layers[s->layer_begin].norm1, m->eps, s->skip_embed ? 0.f : g->embed_scale,
-                           s->T, m->H, m->dtype, st);
-}
+struct SchedGemma2 {
+  const UmbModel* m; const UmbWorkspace* ws; const UmbStep* s; const UmbGemma2* g; hipStream_t st;
+  // prologue: embedding gather, h <- round(h * round(sqrt H)), xn <- gemma_norm(h, input_layernorm)
+  int pro() {
+    CK(embed(m, ws, s, nullptr, nullptr, nullptr, -1, st));
+    return umb_gemma_rmsnorm(ws->xn, ws->h, m->layers[s->layer_begin].norm1, m->eps, s->skip_embed ? 0.f : g->embed_scale,
+                             s->T, m->H, m->dtype, st);
+  }
+  // one Gemma2DecoderLayer: 9 launches (qkv, q/k/v reduce + RoPE + KV append, attention, o, sandwich, gate/up, gelu * up,
+  // down, sandwich).  next_norm: the next layer's input_layernorm or the final norm (NULL: leave h only)
+  int lay(const UmbLayer& ly, int l, const void* next_norm) {
+    const int T = s->T, dt = m->dtype;
+    const KV kv = kv_slabs(m, l);
+    const UmbGemma2Norms& gn = g->norms[l];
+    if (ly.qkv_bias || !gn.pre_ff || !gn.post_ff) return UMB_EINVAL;
+    CK(lin(ly.qkv, ws->xn, m->H, ws->partial, T, dt, st, 0, nullptr));
+    CK(umb_reduce_qkv_rope(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
+                           m->rope_sin, ws->q, kv.k, kv.vt, /*paired=*/1, nullptr, dt, st));
+    const int win = (g->window > 0 && (l & 1) == g->slide_parity) ? g->window : 0;
+    CK(umb_tree_attn_gemma2(ws->attn, ws->q, kv.k, kv.vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
+                            s->n_mask_keys, T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_splits, m->attn_scale, g->attn_softcap,
+                            ws->pos, win, ws->attn_counters, dt, st));
+    CK(lin(ly.o, ws->attn, m->Hq * m->D, ws->partial, T, dt, st, 0, nullptr, true));
+    CK(umb_gemma_sandwich(ws->partial, eff_s(ly.o, T, true), T, m->H, ws->h, ws->xn, ly.norm2, gn.pre_ff, m->eps, dt, st));
+    // gate/up: a plain [gate; up] stack (not interleaved), split-K partials, GELU * up in the reduce
+    CK(lin(ly.gu, ws->xn, m->H, ws->partial, T, dt, st, 0, nullptr));
+    CK(umb_reduce_gelu_mul(ws->partial, eff_s(ly.gu, T), T, m->I, ws->act, dt, st));
+    CK(lin(ly.down, ws->act, m->I, ws->partial, T, dt, st, 0, nullptr, true));
+    CK(umb_gemma_sandwich(ws->partial, eff_s(ly.down, T, true), T, m->H, ws->h, next_norm ? ws->xn : nullptr, gn.post_ff,
+                          next_norm, m->eps, dt, st));
+    return UMB_OK;
+  }
+  int hd() {
+    if (s->head_from >= s->T) return UMB_OK;
+    CK(head_xn(m, ws, s, st));
+    if (g->final_softcap > 0.f)
+      CK(umb_logit_softcap(ws->logits, (int64_t)(s->T - s->head_from) * m->lm_head.N, g->final_softcap, st));
+    return UMB_OK;
+  }
+};
 
-// one Gemma2DecoderLayer: 9 launches (qkv, q/k/v reduce + RoPE + KV append, attention, o, sandwich, gate/up, gelu * up,
-// down, sandwich).  next_norm: the next layer's input_layernorm or the final norm (NULL: leave h only)
-static int layer_gemma2(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbGemma2* g, const UmbLayer& ly,
-                        int l, const void* next_norm, hipStream_t st) {
-  const int T = s->T, dt = m->dtype;
-  char* kc = (char*)m->k_cache + (size_t)l * m->Hkv * m->Lmax * m->D * 2;
-  char* vt = (char*)m->vt_cache + (size_t)l * m->Hkv * VT_LD(m->Lmax) * m->D * 2;
-  const UmbGemma2Norms& gn = g->norms[l];
-  if (ly.qkv_bias || !gn.pre_ff || !gn.post_ff) return UMB_EINVAL;
-  CK(lin(ly.qkv, ws->xn, m->H, ws->partial, T, dt, st, 0, nullptr));
-  CK(umb_reduce_qkv_rope(ws->partial, eff_s(ly.qkv, T), T, m->Hq, m->Hkv, m->D, m->Lmax, ws->pos, ws->slot, m->rope_cos,
-                         m->rope_sin, ws->q, kc, vt, /*paired=*/1, nullptr, dt, st));
-  const int win = (g->window > 0 && (l & 1) == g->slide_parity) ? g->window : 0;
-  CK(umb_tree_attn_gemma2(ws->attn, ws->q, kc, vt, ws->attn_po, ws->attn_ml, ws->prefix, s->mask_bits, s->mask_words,
-                          s->n_mask_keys, T, m->Hq, m->Hkv, m->D, m->Lmax, ws->attn_splits, m->attn_scale, g->attn_softcap,
-                          ws->pos, win, ws->attn_counters, dt, st));
-  CK(lin(ly.o, ws->attn, m->Hq * m->D, ws->partial, T, dt, st, 0, nullptr, true));
-  CK(umb_gemma_sandwich(ws->partial, eff_s(ly.o, T, true), T, m->H, ws->h, ws->xn, ly.norm2, gn.pre_ff, m->eps, dt, st));
-  // gate/up: a plain [gate; up] stack (not interleaved), split-K partials, GELU * up in the reduce
-  CK(lin(ly.gu, ws->xn, m->H, ws->partial, T, dt, st, 0, nullptr));
-  CK(umb_reduce_gelu_mul(ws->partial, eff_s(ly.gu, T), T, m->I, ws->act, dt, st));
-  CK(lin(ly.down, ws->act, m->I, ws->partial, T, dt, st, 0, nullptr, true));
-  CK(umb_gemma_sandwich(ws->partial, eff_s(ly.down, T, true), T, m->H, ws->h, next_norm ? ws->xn : nullptr, gn.post_ff,
-                        next_norm, m->eps, dt, st));
-  return UMB_OK;
-}
-
-static int head_gemma2(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbGemma2* g, hipStream_t st) {
-  if (s->head_from >= s->T) return UMB_OK;
-  const int rows = s->T - s->head_from;
-  const char* xn = (const char*)ws->xn + (size_t)s->head_from * m->H * 2;
-  CK(lin(m->lm_head, xn, m->H, ws->logits, rows, m->dtype, st, /*EPI_ROUND*/1, nullptr));
-  if (g->final_softcap > 0.f) CK(umb_logit_softcap(ws->logits, (int64_t)rows * m->lm_head.N, g->final_softcap, st));
-  return UMB_OK;
-}
-
-static inline bool gemma2_ok(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbGemma2* g) {
-  if (m->lm_head.awq == 2 || fp8_layers(m, s)) return false;           // FP8 linears: Llama / Qwen3 forwards only
-  return g && g->norms && ws->fused == 0 && s->layer_begin == 0 && s->layer_end == m->L && !s->skip_embed &&
-         g->window >= 0 && (g->slide_parity == 0 || g->slide_parity == 1);
+// whole model only; FP8 linears: Llama / Qwen3 forwards only
+static int gemma2_forward(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbGemma2* g, const UmbOffload* off,
+                          hipStream_t st) {
+  if (fp8_refused(m, ws, s, /*plain=*/false)) return UMB_EINVAL;
+  if (!g || !g->norms || ws->fused != 0 || s->layer_begin != 0 || s->layer_end != m->L || s->skip_embed || g->window < 0 ||
+      (g->slide_parity != 0 && g->slide_parity != 1))
+    return UMB_EINVAL;
+  SchedGemma2 sc = {m, ws, s, g, st};
+  return forward_loop(m, s, off, st, sc);
 }
 
 extern "C" int umb_model_forward_gemma2(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbGemma2* g,
                                         hipStream_t st) {
-  if (!gemma2_ok(m, ws, s, g)) return UMB_EINVAL;
-  CK(prologue_gemma2(m, ws, s, g, st));
-  for (int l = 0; l < m->L; ++l) {
-    const void* nn = l + 1 < m->L ? m->layers[l + 1].norm1 : m->final_norm;
-    CK(layer_gemma2(m, ws, s, g, m->layers[l], l, nn, st));
-  }
-  return head_gemma2(m, ws, s, g, st);
+  return gemma2_forward(m, ws, s, g, nullptr, st);
 }
 
 extern "C" int umb_model_forward_gemma2_offload(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s,
                                                 const UmbGemma2* g, const UmbOffload* off, hipStream_t st) {
-  if (!gemma2_ok(m, ws, s, g)) return UMB_EINVAL;
-  return offload_forward(
-      m, s, off, st, [&]() { return prologue_gemma2(m, ws, s, g, st); },
-      [&](const UmbLayer& cur, int l, const void* nn) { return layer_gemma2(m, ws, s, g, cur, l, nn, st); },
-      [&]() { return head_gemma2(m, ws, s, g, st); });
+  return gemma2_forward(m, ws, s, g, off, st);
 }
 
 // ---- Qwen3 (HF modeling_qwen3): umb_model_forward's schedule 0 with the per-head q / k RMSNorm in the q/k/v reduce
-// (umb_reduce_qkv_rope_qknorm); the deferred norm and the FM-ordered activations under the rules of model_forward.
-// off == NULL: resident; else the streaming loop of umb_model_forward_offload.
+// (umb_reduce_qkv_rope_qknorm); the deferred norm and the FM-ordered activations under the rules of every schedule-0 forward.
+// Whole model only.  off == NULL: resident; else the streaming loop of umb_model_forward_offload.
 static int qwen3_forward(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbQwen3* q, const UmbOffload* off,
                          hipStream_t st) {
   if (!q || !q->norms || ws->fused != 0 || s->layer_begin != 0 || s->layer_end != m->L || s->skip_embed || m->D > 256)
     return UMB_EINVAL;
   for (int l = 0; l < m->L; ++l)
     if (!q->norms[l].q_norm || !q->norms[l].k_norm) return UMB_EINVAL;
-  if (fp8_refused(m, ws, s) || (off && fp8_layers(m, s))) return UMB_EINVAL;
-  const int fm = split_fm_tt(m, ws, s, nullptr);
-  const bool df = use_defer(m, ws, s, nullptr);
-  int sg = 4;
-  auto pro = [&]() {
-    return df ? prologue_defer(m, ws, s, m->layers[0].norm1, fm, &sg, st) : prologue(m, ws, s, m->layers[0].norm1, st, fm);
-  };
-  auto lay = [&](const UmbLayer& cur, int l, const void* nn) {
-    return df ? layer_split_defer(m, ws, s, cur, l, nn, &sg, st, fm, l + 1 < m->L, &q->norms[l], q->qk_eps)
-              : layer_split(m, ws, s, cur, l, nn, st, nullptr, fm, l + 1 < m->L, &q->norms[l], q->qk_eps);
-  };
-  auto hd = [&]() { return df ? head_defer(m, ws, s, sg, st) : head(m, ws, s, st); };
-  if (off) return offload_forward(m, s, off, st, pro, lay, hd);
-  CK(pro());
-  for (int l = 0; l < m->L; ++l) CK(lay(m->layers[l], l, l + 1 < m->L ? m->layers[l + 1].norm1 : m->final_norm));
-  return hd();
+  return llama_forward(m, ws, s, nullptr, off, q, st);
 }
 
 extern "C" int umb_model_forward_qwen3(const UmbModel* m, const UmbWorkspace* ws, const UmbStep* s, const UmbQwen3* q,

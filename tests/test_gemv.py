@@ -2,7 +2,8 @@
 
 Each epilogue against an fp32 torch restatement of the reference lines it fuses (llama.py:75-114 residual adds / SiLU * up,
 model_utils.py:17-64 RoPE + rmsnorm factor, cache.py:53-65 KV append) and against the low-latency MFMA kernel on the same
-weights (q / K / V^T contents, up to the fp32 accumulation order); bitwise batch invariance; the row repack."""
+weights (q / K / V^T contents, up to the fp32 accumulation order); bitwise batch invariance; the row repack.
+Bit-exact coverage of every launch shape and epilogue of gv_kernel: tests/test_lowlat_exact.py."""
 import pytest
 import torch
 

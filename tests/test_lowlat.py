@@ -6,6 +6,7 @@ on how many rows share the launch, nor on the token tiling), and the FM activati
 Tolerances: dense -- fp32 accumulation order only (1e-4 of the row scale).  AWQ int4 -- the folded form computes
 s * sum_k (q - z) x_k in fp32 without rounding (q - z) * s to fp16 first, so it differs from the dequantise-then-matmul
 oracle by at most the fp16 rounding of the weights: 2^-11 relative per weight, < 2e-3 of the row scale after the sum.
+Bit-exact coverage of every plan variable and epilogue of ll_gemm_kernel: tests/test_lowlat_exact.py.
 """
 import ctypes as C
 

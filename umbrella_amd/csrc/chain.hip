@@ -681,7 +681,7 @@ __global__ __launch_bounds__(256) void draft_chain_kernel(const char* w_o, const
         const float a0 = rnd_prod<P>(acc[2 * pr], iv), b0 = rnd_prod<P>(acc[2 * pr + 1], iv);
         if (head < a.Hq + a.Hkv) {
           const float cl = P::to_f(rc[pr][0]), chh = P::to_f(rc[pr][1]), sl_ = P::to_f(rc[pr][2]), sh = P::to_f(rc[pr][3]);
-          const float lo0 = rnd<P>(mul_rnd<P>(a0, cl) + mul_rnd<P>(-b0, sl_));
+          const float lo0 = rnd<P>(mul_rnd<P>(a0, cl) - mul_rnd<P>(b0, sl_));
           const float hi0 = rnd<P>(mul_rnd<P>(b0, chh) + mul_rnd<P>(a0, sh));
           if (head < a.Hq) {
             u16* dst = a.q_out + ((long)tl * a.Hq + head) * D;

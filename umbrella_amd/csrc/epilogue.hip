@@ -300,7 +300,7 @@ __global__ __launch_bounds__(64) void reduce_qkv_rope_kernel(const float* __rest
       // rotate-half RoPE in the model dtype (each product and the sum are rounded, as eager torch does)
       const float c0 = P::to_f(cosT[(long)p * D + d]), c1 = P::to_f(cosT[(long)p * D + d + half]);
       const float s0 = P::to_f(sinT[(long)p * D + d]), s1 = P::to_f(sinT[(long)p * D + d + half]);
-      const float o0 = rnd<P>(mul_rnd<P>(a, c0) + mul_rnd<P>(-b, s0));
+      const float o0 = rnd<P>(mul_rnd<P>(a, c0) - mul_rnd<P>(b, s0));
       const float o1 = rnd<P>(mul_rnd<P>(b, c1) + mul_rnd<P>(a, s1));
       if (head < Hq) {
         u16* qo = q_out + ((long)t * Hq + head) * D;
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(64) void reduce_qkv_rope_qknorm_kernel(const float*
     const float zb = mul_rnd<P>(P::to_f(w[d + half]), rnd_prod<P>(b[i], r));
     const float c0 = P::to_f(cosT[(long)p * D + d]), c1 = P::to_f(cosT[(long)p * D + d + half]);
     const float s0 = P::to_f(sinT[(long)p * D + d]), s1 = P::to_f(sinT[(long)p * D + d + half]);
-    const float o0 = rnd<P>(mul_rnd<P>(za, c0) + mul_rnd<P>(-zb, s0));
+    const float o0 = rnd<P>(mul_rnd<P>(za, c0) - mul_rnd<P>(zb, s0));
     const float o1 = rnd<P>(mul_rnd<P>(zb, c1) + mul_rnd<P>(za, s1));
     if (head < Hq) {
       u16* qo = q_out + ((long)t * Hq + head) * D;
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(64) void rope_inplace_kernel(u16* __restrict__ q, u
     const float c0 = P::to_f(cosT[cb + d]), c1 = P::to_f(cosT[cb + d + half]);
     const float s0 = P::to_f(sinT[cb + d]), s1 = P::to_f(sinT[cb + d + half]);
     // x * cos + rotate_half(x) * sin in the model dtype: every product and the sum are rounded, as eager torch does
-    base[d] = P::from_f(mul_rnd<P>(a, c0) + mul_rnd<P>(-b, s0));
+    base[d] = P::from_f(mul_rnd<P>(a, c0) - mul_rnd<P>(b, s0));
     base[d + half] = P::from_f(mul_rnd<P>(b, c1) + mul_rnd<P>(a, s1));
   }
 }

@@ -703,8 +703,8 @@ __global__ __launch_bounds__(64 * NWV) void skinny_gemm_kernel(const u32x4* __re
         const unsigned sl_ = *reinterpret_cast<const unsigned*>(fx.sinT + cb + m);
         const unsigned sh = *reinterpret_cast<const unsigned*>(fx.sinT + cb + m + half);
         // rotate-half in the model dtype: every product and the sum are rounded (eager torch, model_utils.py:50-51)
-        const float lo0 = rnd<P>(mul_rnd<P>(a0, lo_f<P>(cl)) + mul_rnd<P>(-b0, lo_f<P>(sl_)));
-        const float lo1 = rnd<P>(mul_rnd<P>(a1, hi_f<P>(cl)) + mul_rnd<P>(-b1, hi_f<P>(sl_)));
+        const float lo0 = rnd<P>(mul_rnd<P>(a0, lo_f<P>(cl)) - mul_rnd<P>(b0, lo_f<P>(sl_)));
+        const float lo1 = rnd<P>(mul_rnd<P>(a1, hi_f<P>(cl)) - mul_rnd<P>(b1, hi_f<P>(sl_)));
         const float hi0 = rnd<P>(mul_rnd<P>(b0, lo_f<P>(ch)) + mul_rnd<P>(a0, lo_f<P>(sh)));
         const float hi1 = rnd<P>(mul_rnd<P>(b1, hi_f<P>(ch)) + mul_rnd<P>(a1, hi_f<P>(sh)));
         // q rows are row-major; the K / V^T caches are in fragment order inside a head's slab (common.h: m is even, so the

@@ -228,7 +228,7 @@ __global__ __launch_bounds__(512) void gv_kernel(const u32x4* __restrict__ w, co
         if (head < a.Hq + a.Hkv) {
           const float cl = P::to_f(er[B].cl[r / 2]), ch = P::to_f(er[B].ch[r / 2]);
           const float sl_ = P::to_f(er[B].sl[r / 2]), sh = P::to_f(er[B].sh[r / 2]);
-          const float lo0 = rnd<P>(mul_rnd<P>(a0, cl) + mul_rnd<P>(-b0, sl_));
+          const float lo0 = rnd<P>(mul_rnd<P>(a0, cl) - mul_rnd<P>(b0, sl_));
           const float hi0 = rnd<P>(mul_rnd<P>(b0, ch) + mul_rnd<P>(a0, sh));
           // slot_t is trusted here (the model runtime derives it from the engine's guarded state: HipEngine.step refuses
           // a tree that would pass max_length); a per-store range check costs this kernel 24 B of scratch per lane

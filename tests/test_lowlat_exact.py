@@ -484,9 +484,10 @@ def xs_for(K, dev, nnz=None, nonneg=False):
     return x.abs() if nonneg else x
 
 
-def _fx(**kw):
+def _fx(cls=None, **kw):
+    """a filled UmbGemmLL (cls: another argument struct of _lib, e.g. UmbGemmFused); tensors are kept alive on the struct"""
     from umbrella_amd import _lib
-    fx = _lib.UmbGemmLL()
+    fx = (cls or _lib.UmbGemmLL)()
     keep = []
     for k, v in kw.items():
         if isinstance(v, torch.Tensor):

@@ -20,6 +20,7 @@
 // bounded by the 100 MHz wall clock; a give-up sets status != 0, poisons nothing further and lets the launch finish.
 #include "../../include/umbrella_hip.h"
 #include "common.h"
+#include "qkv_epilogue.h"
 #include <type_traits>
 
 typedef __attribute__((address_space(1))) unsigned long long gu64;
@@ -673,29 +674,18 @@ __global__ __launch_bounds__(256) void draft_chain_kernel(const char* w_o, const
       }
       if (!fin) continue;
       const float iv = inv;
-      const int D = a.D, half = D / 2;
+      const QkvDst q = {a.pos, a.slot, a.cosT, a.sinT, a.q_out, a.kc, a.vt, a.Hq, a.Hkv, a.D, a.Lmax};
+      const int D = q.D;
 #pragma unroll
       for (int pr = 0; pr < 2; ++pr) {
         const int n = qrows * cu + 4 * sa_q + 2 * pr;
         const int head = n / D, dp = n % D, m = dp >> 1;
         const float a0 = rnd_prod<P>(acc[2 * pr], iv), b0 = rnd_prod<P>(acc[2 * pr + 1], iv);
-        if (head < a.Hq + a.Hkv) {
+        if (head < q.Hq + q.Hkv) {                   // slot_t is trusted, as in gv_kernel
           const float cl = P::to_f(rc[pr][0]), chh = P::to_f(rc[pr][1]), sl_ = P::to_f(rc[pr][2]), sh = P::to_f(rc[pr][3]);
-          const float lo0 = rnd<P>(mul_rnd<P>(a0, cl) - mul_rnd<P>(b0, sl_));
-          const float hi0 = rnd<P>(mul_rnd<P>(b0, chh) + mul_rnd<P>(a0, sh));
-          if (head < a.Hq) {
-            u16* dst = a.q_out + ((long)tl * a.Hq + head) * D;
-            dst[m] = P::from_f(lo0);
-            dst[m + half] = P::from_f(hi0);
-          } else {
-            u16* dst = a.kc + (long)(head - a.Hq) * a.Lmax * D;
-            dst[kc_off(slot_t, m, D)] = P::from_f(lo0);
-            dst[kc_off(slot_t, m + half, D)] = P::from_f(hi0);
-          }
+          qk_store_pair(q, head, m, tl, slot_t, rope_rotate<P>(a0, b0, cl, chh, sl_, sh));
         } else {
-          u16* dst = a.vt + (long)(head - a.Hq - a.Hkv) * D * VT_LD(a.Lmax);
-          dst[vt_off(dp, slot_t, D)] = P::from_f(a0);
-          dst[vt_off(dp + 1, slot_t, D)] = P::from_f(b0);
+          v_store2<P>(q, head, dp, dp + 1, slot_t, a0, b0);
         }
       }
     }
@@ -930,14 +920,14 @@ extern "C" int umb_draft_chain(const UmbChain* c, int dtype, hipStream_t st) {
   a.attn = (const u16*)c->attn; a.h = (u16*)c->h; a.hw = (u16*)c->hw; a.ssq = c->ssq;
   a.norm2 = (const u16*)c->norm2; a.next_norm = (const u16*)c->next_norm;
   a.pos = c->pos; a.slot = c->slot; a.cosT = (const u16*)c->cosT; a.sinT = (const u16*)c->sinT; a.q_out = (u16*)c->q_out;
-  a.kc = (u16*)c->k_cache; a.vt = (u16*)c->vt_cache;
+  a.kc = (u16*)c->k_cache; a.vt = (u16*)c->vt_cache; a.Hq = c->Hq; a.Hkv = c->Hkv; a.D = c->D; a.Lmax = c->Lmax;
   char* xb = (char*)c->xchg;
   const size_t gh = (size_t)c->Tmax * (c->H / 2) * 8, ga = (size_t)c->Tmax * (c->I / 2) * 8;
   a.g_h1 = (gu64*)xb; a.g_act = (gu64*)(xb + gh); a.g_h2 = (gu64*)(xb + gh + ga);
   a.epoch = (gu32*)(xb + 2 * gh + ga); a.status = (gu32*)(xb + 2 * gh + ga + 64);
   if (T > c->Tmax) return UMB_EINVAL;
   a.T = T; a.R = chain_ring(T); a.front = c->front; a.tail = c->tail; a.H = c->H; a.I = c->I; a.NQKV = c->NQKV;
-  a.ssq_stride = c->ssq_stride; a.ssq_groups_in = c->ssq_groups_in; a.Hq = c->Hq; a.Hkv = c->Hkv; a.D = c->D; a.Lmax = c->Lmax;
+  a.ssq_stride = c->ssq_stride; a.ssq_groups_in = c->ssq_groups_in;
   a.eps = c->eps;
   a.off_sth = (unsigned)a.R * CH_SLOT; a.off_sta = a.off_sth + (unsigned)T * 4096u;
   const unsigned off_flags = a.off_sta + (unsigned)T * 16384u;

@@ -8,6 +8,7 @@
 //   q/k/v view + RoPE at tree positions (model_utils.py:17-52) + KV append (attn/cache.py:53-65)
 //   embedding gather (F.embedding, llama.py:124)
 #include "common.h"
+#include "qkv_epilogue.h"
 // split-K partials are read exactly once, by a kernel on other XCDs than their writers: non-temporal loads (70B layer at T = 13:
 // -0.7 us over its two residual reduces; profiles/r05_handoff_stores.txt)
 #define LDP(p) __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p))
@@ -261,6 +262,7 @@ __global__ __launch_bounds__(64) void reduce_qkv_rope_kernel(const float* __rest
   const int N = (Hq + 2 * Hkv) * D;
   const int half = D / 2;
   const int p = pos[t], sl = slot[t];
+  const QkvDst q = {pos, slot, cosT, sinT, q_out, kc, vt, Hq, Hkv, D, Lmax};
   // low-latency schedule: the GEMM ran on h * w (norm weight folded by the producer); the per-token 1/rms from the
   // producer's sums of squares is applied to the reduced outputs here (it commutes with the matmul)
   float inv = 1.f;
@@ -297,22 +299,11 @@ __global__ __launch_bounds__(64) void reduce_qkv_rope_kernel(const float* __rest
     }
     a = rnd<P>(a); b = rnd<P>(b);
     if (head < Hq + Hkv) {
-      // rotate-half RoPE in the model dtype (each product and the sum are rounded, as eager torch does)
       const float c0 = P::to_f(cosT[(long)p * D + d]), c1 = P::to_f(cosT[(long)p * D + d + half]);
       const float s0 = P::to_f(sinT[(long)p * D + d]), s1 = P::to_f(sinT[(long)p * D + d + half]);
-      const float o0 = rnd<P>(mul_rnd<P>(a, c0) - mul_rnd<P>(b, s0));
-      const float o1 = rnd<P>(mul_rnd<P>(b, c1) + mul_rnd<P>(a, s1));
-      if (head < Hq) {
-        u16* qo = q_out + ((long)t * Hq + head) * D;
-        qo[d] = P::from_f(o0); qo[d + half] = P::from_f(o1);
-      } else {
-        u16* ko = kc + (long)(head - Hq) * Lmax * D;            // fragment order inside the head's slab (common.h)
-        ko[kc_off(sl, d, D)] = P::from_f(o0); ko[kc_off(sl, d + half, D)] = P::from_f(o1);
-      }
+      qk_store_pair(q, head, d, t, sl, rope_rotate<P>(a, b, c0, c1, s0, s1));
     } else {
-      u16* vo = vt + (long)(head - Hq - Hkv) * D * VT_LD(Lmax);
-      vo[vt_off(d, sl, D)] = P::from_f(a);
-      vo[vt_off(d + half, sl, D)] = P::from_f(b);
+      v_store2<P>(q, head, d, d + half, sl, a, b);
     }
   }
 }
@@ -384,12 +375,12 @@ __global__ __launch_bounds__(64) void reduce_qkv_rope_qknorm_kernel(const float*
     }
     a[i] = x; b[i] = y;
   }
+  const QkvDst q = {pos, slot, cosT, sinT, q_out, kc, vt, Hq, Hkv, D, Lmax};
   if (!rot) {
-    u16* vo = vt + (long)(head - Hq - Hkv) * D * VT_LD(Lmax);
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int d = threadIdx.x + 64 * i;
-      if (d < half) { vo[vt_off(d, sl, D)] = P::from_f(a[i]); vo[vt_off(d + half, sl, D)] = P::from_f(b[i]); }
+      if (d < half) v_store2<P>(q, head, d, d + half, sl, a[i], b[i]);
     }
     return;
   }
@@ -411,15 +402,7 @@ __global__ __launch_bounds__(64) void reduce_qkv_rope_qknorm_kernel(const float*
     const float zb = mul_rnd<P>(P::to_f(w[d + half]), rnd_prod<P>(b[i], r));
     const float c0 = P::to_f(cosT[(long)p * D + d]), c1 = P::to_f(cosT[(long)p * D + d + half]);
     const float s0 = P::to_f(sinT[(long)p * D + d]), s1 = P::to_f(sinT[(long)p * D + d + half]);
-    const float o0 = rnd<P>(mul_rnd<P>(za, c0) - mul_rnd<P>(zb, s0));
-    const float o1 = rnd<P>(mul_rnd<P>(zb, c1) + mul_rnd<P>(za, s1));
-    if (head < Hq) {
-      u16* qo = q_out + ((long)t * Hq + head) * D;
-      qo[d] = P::from_f(o0); qo[d + half] = P::from_f(o1);
-    } else {
-      u16* ko = kc + (long)(head - Hq) * Lmax * D;            // fragment order inside the head's slab (common.h)
-      ko[kc_off(sl, d, D)] = P::from_f(o0); ko[kc_off(sl, d + half, D)] = P::from_f(o1);
-    }
+    qk_store_pair(q, head, d, t, sl, rope_rotate<P>(za, zb, c0, c1, s0, s1));
   }
 }
 
@@ -489,9 +472,9 @@ __global__ __launch_bounds__(64) void rope_inplace_kernel(u16* __restrict__ q, u
     const float a = P::to_f(base[d]), b = P::to_f(base[d + half]);
     const float c0 = P::to_f(cosT[cb + d]), c1 = P::to_f(cosT[cb + d + half]);
     const float s0 = P::to_f(sinT[cb + d]), s1 = P::to_f(sinT[cb + d + half]);
-    // x * cos + rotate_half(x) * sin in the model dtype: every product and the sum are rounded, as eager torch does
-    base[d] = P::from_f(mul_rnd<P>(a, c0) - mul_rnd<P>(b, s0));
-    base[d + half] = P::from_f(mul_rnd<P>(b, c1) + mul_rnd<P>(a, s1));
+    const RopePair r = rope_rotate<P>(a, b, c0, c1, s0, s1);
+    base[d] = r.lo;
+    base[d + half] = r.hi;
   }
 }
 

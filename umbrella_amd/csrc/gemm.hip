@@ -42,11 +42,7 @@
 //          rows (2m, 2m+1) <- (m, m + D/2)                                  -> rotate-half RoPE in the GEMM epilogue
 __host__ __device__ __forceinline__ int rowmap(int n, int N, int mode, int D, int rope_heads) {
   if (mode == 1) return (n & 1) ? N / 2 + (n >> 1) : (n >> 1);
-  if (mode == 2) {
-    const int head = n / D, dp = n % D;
-    if (head >= rope_heads) return n;
-    return head * D + ((dp & 1) ? (dp >> 1) + D / 2 : (dp >> 1));
-  }
+  if (mode == 2) return qk_rowmap(n, D, rope_heads);
   return n;
 }
 
@@ -654,20 +650,7 @@ __global__ __launch_bounds__(64 * NWV) void skinny_gemm_kernel(const u32x4* __re
       float sq = 0.f;
       if (active && tok < T) {
         const long off = (long)tok * N + nt0 * 16 + g * 4;
-        const uint2 hr = *reinterpret_cast<const uint2*>(fx.h + off);
-        const f32x4 v = acc[0][tt];
-        const float h0 = rnd<P>(rnd<P>(v[0]) + lo_f<P>(hr.x)), h1 = rnd<P>(rnd<P>(v[1]) + hi_f<P>(hr.x));
-        const float h2v = rnd<P>(rnd<P>(v[2]) + lo_f<P>(hr.y)), h3 = rnd<P>(rnd<P>(v[3]) + hi_f<P>(hr.y));
-        uint2 o;
-        o.x = pack2<P>(h0, h1); o.y = pack2<P>(h2v, h3);
-        *reinterpret_cast<uint2*>(fx.h + off) = o;
-        if (fx.norm_w) {
-          const uint2 w = *reinterpret_cast<const uint2*>(fx.norm_w + nt0 * 16 + g * 4);
-          uint2 ow;
-          ow.x = pack2<P>(h0 * lo_f<P>(w.x), h1 * hi_f<P>(w.x)); ow.y = pack2<P>(h2v * lo_f<P>(w.y), h3 * hi_f<P>(w.y));
-          *reinterpret_cast<uint2*>(fx.hw + off) = ow;
-        }
-        sq = h0 * h0 + h1 * h1 + h2v * h2v + h3 * h3;
+        sq = resid_step4<P>(acc[0][tt], fx.h + off, fx.norm_w, nt0 * 16 + g * 4, fx.hw + off);   // hw row-major
       }
       sq += __shfl_xor(sq, 16, 64);
       sq += __shfl_xor(sq, 32, 64);
@@ -685,7 +668,8 @@ __global__ __launch_bounds__(64 * NWV) void skinny_gemm_kernel(const u32x4* __re
   // EPI_QKV: rows were permuted at load so (2m, 2m+1) of a q/k head are RoPE partners (m, m + D/2)
   if (!active) return;
   {
-    const int D = fx.D, half = D / 2;
+    const QkvDst& q = fx.qkv;
+    const int D = q.D, half = D / 2;
     const int n = nt0 * 16 + g * 4;
     const int head = n / D, dp = n % D, m = dp >> 1;
 #pragma unroll
@@ -695,29 +679,18 @@ __global__ __launch_bounds__(64 * NWV) void skinny_gemm_kernel(const u32x4* __re
       f32x4 v = acc[0][tt];
       v *= inv[tt];
       const float a0 = rnd<P>(v[0]), b0 = rnd<P>(v[1]), a1 = rnd<P>(v[2]), b1 = rnd<P>(v[3]);
-      const int sl = fx.slot[tok];
-      if (head < fx.Hq + fx.Hkv) {
-        const long cb = (long)fx.pos[tok] * D;
-        const unsigned cl = *reinterpret_cast<const unsigned*>(fx.cosT + cb + m);
-        const unsigned ch = *reinterpret_cast<const unsigned*>(fx.cosT + cb + m + half);
-        const unsigned sl_ = *reinterpret_cast<const unsigned*>(fx.sinT + cb + m);
-        const unsigned sh = *reinterpret_cast<const unsigned*>(fx.sinT + cb + m + half);
-        // rotate-half in the model dtype: every product and the sum are rounded (eager torch, model_utils.py:50-51)
-        const float lo0 = rnd<P>(mul_rnd<P>(a0, lo_f<P>(cl)) - mul_rnd<P>(b0, lo_f<P>(sl_)));
-        const float lo1 = rnd<P>(mul_rnd<P>(a1, hi_f<P>(cl)) - mul_rnd<P>(b1, hi_f<P>(sl_)));
-        const float hi0 = rnd<P>(mul_rnd<P>(b0, lo_f<P>(ch)) + mul_rnd<P>(a0, lo_f<P>(sh)));
-        const float hi1 = rnd<P>(mul_rnd<P>(b1, hi_f<P>(ch)) + mul_rnd<P>(a1, hi_f<P>(sh)));
-        // q rows are row-major; the K / V^T caches are in fragment order inside a head's slab (common.h: m is even, so the
-        // pair (m, m + 1) stays one 4-byte store)
-        u16* dlo = (head < fx.Hq) ? fx.q_out + ((long)tok * fx.Hq + head) * D + m
-                                  : fx.kc + (long)(head - fx.Hq) * fx.Lmax * D + kc_off(sl, m, D);
-        u16* dhi = (head < fx.Hq) ? dlo + half : fx.kc + (long)(head - fx.Hq) * fx.Lmax * D + kc_off(sl, m + half, D);
-        *reinterpret_cast<unsigned*>(dlo) = pack2<P>(lo0, lo1);
-        *reinterpret_cast<unsigned*>(dhi) = pack2<P>(hi0, hi1);
+      const int sl = q.slot[tok];
+      if (head < q.Hq + q.Hkv) {
+        const long cb = (long)q.pos[tok] * D;
+        const unsigned cl = *reinterpret_cast<const unsigned*>(q.cosT + cb + m);
+        const unsigned ch = *reinterpret_cast<const unsigned*>(q.cosT + cb + m + half);
+        const unsigned sl_ = *reinterpret_cast<const unsigned*>(q.sinT + cb + m);
+        const unsigned sh = *reinterpret_cast<const unsigned*>(q.sinT + cb + m + half);
+        const u16 lo0 = rope_lo<P>(a0, b0, lo_f<P>(cl), lo_f<P>(sl_)), lo1 = rope_lo<P>(a1, b1, hi_f<P>(cl), hi_f<P>(sl_));
+        const u16 hi0 = rope_hi<P>(a0, b0, lo_f<P>(ch), lo_f<P>(sh)), hi1 = rope_hi<P>(a1, b1, hi_f<P>(ch), hi_f<P>(sh));
+        qk_store_pairs2(q, head, m, tok, sl, lo0, lo1, hi0, hi1);
       } else {
-        u16* vb = fx.vt + (long)(head - fx.Hq - fx.Hkv) * D * VT_LD(fx.Lmax);
-        vb[vt_off(dp, sl, D)] = P::from_f(a0); vb[vt_off(dp + 1, sl, D)] = P::from_f(b0);
-        vb[vt_off(dp + 2, sl, D)] = P::from_f(a1); vb[vt_off(dp + 3, sl, D)] = P::from_f(b1);
+        v_store4<P>(q, head, dp, sl, a0, b0, a1, b1);
       }
     }
   }
@@ -1485,9 +1458,9 @@ static int launch_tt(const void* wp, const void* meta, const u16* x, int ldx, fl
     if (fx.ssq_out) fx.ssq_out += (long)t0 * fx.ssq_out_stride;
     if (fx.h) fx.h += (long)t0 * N;
     if (fx.hw) fx.hw += (long)t0 * N;
-    if (fx.pos) fx.pos += t0;
-    if (fx.slot) fx.slot += t0;
-    if (fx.q_out) fx.q_out += (long)t0 * fx.Hq * fx.D;
+    if (fx.qkv.pos) fx.qkv.pos += t0;
+    if (fx.qkv.slot) fx.qkv.slot += t0;
+    if (fx.qkv.q_out) fx.qkv.q_out += (long)t0 * fx.qkv.Hq * fx.qkv.D;
     int rc;
     // k-blocks per LDS chunk (= half the weight ring) by token tiles.  Fewer = fewer registers = more waves per SIMD;
     // measured optima below (UMB_CB / UMB_CB2 / UMB_CB4 override: experiments)
@@ -1536,16 +1509,15 @@ extern "C" int umb_gemm_fused(void* out, const void* x, int ldx, const void* wpa
     fx.ssq_stride = fxc->pad0; fx.x_fm = fxc->pad1 & 1; fx.out_fm = (fxc->pad1 >> 1) & 1;
     fx.ssq_in = fxc->ssq_in; fx.ssq_groups = fxc->ssq_groups; fx.ssq_dim = fxc->ssq_dim; fx.eps = fxc->eps;
     fx.counters = fxc->counters; fx.h = (u16*)fxc->h; fx.hw = (u16*)fxc->hw; fx.norm_w = (const u16*)fxc->norm_w;
-    fx.ssq_out = fxc->ssq_out; fx.ssq_out_stride = fxc->ssq_out_stride; fx.pos = fxc->pos; fx.slot = fxc->slot; fx.cosT = (const u16*)fxc->cosT;
-    fx.sinT = (const u16*)fxc->sinT; fx.q_out = (u16*)fxc->q_out; fx.kc = (u16*)fxc->k_cache; fx.vt = (u16*)fxc->vt_cache;
-    fx.Hq = fxc->Hq; fx.Hkv = fxc->Hkv; fx.D = fxc->D; fx.Lmax = fxc->Lmax;
+    fx.ssq_out = fxc->ssq_out; fx.ssq_out_stride = fxc->ssq_out_stride; fx.qkv = qkv_dst(*fxc);
   }
   if (epi >= EPI_QKV) {
     if (R != 1 || N % 64 || (S > 1 && !fx.counters)) return UMB_EINVAL;
     if (epi == EPI_RESID && (!fx.h || (fx.ssq_out && fx.ssq_out_stride < N / 64))) return UMB_EINVAL;
-    if (epi == EPI_QKV && (!fx.pos || !fx.slot || !fx.q_out || !fx.kc || !fx.vt || fx.D % 4 || (fx.ssq_in && fx.ssq_groups % 4)))
+    const QkvDst& q = fx.qkv;
+    if (epi == EPI_QKV && (!q.pos || !q.slot || !q.q_out || !q.kc || !q.vt || q.D % 4 || (fx.ssq_in && fx.ssq_groups % 4)))
       return UMB_EINVAL;
-    if (epi == EPI_QKV && (fx.D % 32 || fx.Lmax % 32 || fx.Lmax < 32)) return UMB_EINVAL;   // fragment-ordered caches: whole tiles
+    if (epi == EPI_QKV && (q.D % 32 || q.Lmax % 32 || q.Lmax < 32)) return UMB_EINVAL;   // fragment-ordered caches: whole tiles
   }
   if (fx.ssq_in && (fx.ssq_groups % 4 || fx.ssq_stride % 4)) return UMB_EINVAL;
   if ((fx.x_fm || fx.out_fm) && T > 64) return UMB_EINVAL;      // FM buffers hold one launch of <= 64 tokens

@@ -3,6 +3,7 @@
 // share: the exact int4 dequant and the direct epilogue.
 #pragma once
 #include "common.h"
+#include "qkv_epilogue.h"
 
 enum { EPI_PARTIAL = 0, EPI_ROUND = 1, EPI_SILU = 2, EPI_QKV = 3, EPI_RESID = 4 };
 
@@ -19,8 +20,7 @@ struct GemmFused {
   const float* ssq_in; int ssq_groups; float ssq_dim; float eps;
   unsigned* counters;
   u16* h; u16* hw; const u16* norm_w; float* ssq_out; int ssq_out_stride;    // epi 4
-  const int* pos; const int* slot; const u16* cosT; const u16* sinT;          // epi 3
-  u16* q_out; u16* kc; u16* vt; int Hq, Hkv, D, Lmax;
+  QkvDst qkv;                                                                // epi 3
 };
 
 

@@ -13,6 +13,7 @@
 // write hw = h * w and per-workgroup sums of squares, consumers scale their outputs by rsqrt(mean + eps).
 #include "../../include/umbrella_hip.h"
 #include "common.h"
+#include "qkv_epilogue.h"
 #include <type_traits>
 
 typedef _Float16 gv_h2 __attribute__((ext_vector_type(2)));
@@ -30,15 +31,8 @@ struct GvArgs {
   void* out;                                   // GV_SILU: act [T][N/2]
   const float* ssq_in; int ssq_groups, ssq_in_stride; float ssq_dim, eps;
   u16* h; u16* hw; const u16* norm_w; float* ssq_out; int ssq_out_stride;      // GV_RESID
-  const int* pos; const int* slot; const u16* cosT; const u16* sinT; u16* q_out; u16* kc; u16* vt; const u16* bias;
-  int Hq, Hkv, D, Lmax, rope_heads;
+  const u16* bias; QkvDst qkv;                                                   // GV_QKV
 };
-
-__device__ __forceinline__ int gv_rowmap_qkv(int n, int D, int rope_heads) {      // packed row -> HF feature (bias lookup)
-  const int head = n / D, dp = n % D;
-  if (head >= rope_heads) return n;
-  return head * D + ((dp & 1) ? (dp >> 1) + D / 2 : (dp >> 1));
-}
 
 // RW rows per wave and pass, KS k-slices of 2048 elements per row (K = KS * 2048), 8 waves = 8 / KS row-group slots.
 // Argument order: the leading scalars are preloaded into SGPRs (-amdgpu-kernarg-preload-count), the streams start at once.
@@ -76,8 +70,8 @@ __global__ __launch_bounds__(512) void gv_kernel(const u32x4* __restrict__ w, co
   }
   int pos_t = 0, slot_t = 0;
   if constexpr (EPI == GV_QKV) {
-    const auto rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<int*>(a.pos), 0, (unsigned)T * 4u, 0x00020000);
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int*>(a.slot), 0, (unsigned)T * 4u, 0x00020000);
+    const auto rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<int*>(a.qkv.pos), 0, (unsigned)T * 4u, 0x00020000);
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int*>(a.qkv.slot), 0, (unsigned)T * 4u, 0x00020000);
     pos_t = (int)__builtin_amdgcn_raw_buffer_load_b32(rp, fin ? tl * 4 : OOB, 0, 0);
     slot_t = (int)__builtin_amdgcn_raw_buffer_load_b32(rs, fin ? tl * 4 : OOB, 0, 0);
   }
@@ -95,8 +89,8 @@ __global__ __launch_bounds__(512) void gv_kernel(const u32x4* __restrict__ w, co
   const auto rh = __builtin_amdgcn_make_buffer_rsrc(a.h, 0, EPI == GV_RESID ? (unsigned)(T * N * 2) : 0u, 0x00020000);
   const auto rnw = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(a.norm_w), 0,
                                                      (EPI == GV_RESID && a.norm_w) ? (unsigned)N * 2u : 0u, 0x00020000);
-  const auto rcos = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(a.cosT), 0, EPI == GV_QKV ? 0x7fffffffu : 0u, 0x00020000);
-  const auto rsin = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(a.sinT), 0, EPI == GV_QKV ? 0x7fffffffu : 0u, 0x00020000);
+  const auto rcos = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(a.qkv.cosT), 0, EPI == GV_QKV ? 0x7fffffffu : 0u, 0x00020000);
+  const auto rsin = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(a.qkv.sinT), 0, EPI == GV_QKV ? 0x7fffffffu : 0u, 0x00020000);
   const auto rbs = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(a.bias), 0,
                                                      (EPI == GV_QKV && a.bias) ? (unsigned)N * 2u : 0u, 0x00020000);
   auto issue = [&](auto bc, int g) {
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(512) void gv_kernel(const u32x4* __restrict__ w, co
       }
     }
     if constexpr (EPI == GV_QKV) {
-      const int D = a.D, half = D / 2;
+      const int D = a.qkv.D, half = D / 2, rope_heads = a.qkv.Hq + a.qkv.Hkv;
 #pragma unroll
       for (int r = 0; r < RW; r += 2) {
         const int n = row0 + r, m = (n % D) >> 1;
@@ -124,8 +118,8 @@ __global__ __launch_bounds__(512) void gv_kernel(const u32x4* __restrict__ w, co
         er[B].ch[r / 2] = __builtin_amdgcn_raw_buffer_load_b16(rcos, fin ? cb + half * 2 : OOB, 0, 0);
         er[B].sl[r / 2] = __builtin_amdgcn_raw_buffer_load_b16(rsin, cb, 0, 0);
         er[B].sh[r / 2] = __builtin_amdgcn_raw_buffer_load_b16(rsin, fin ? cb + half * 2 : OOB, 0, 0);
-        er[B].bs[r] = __builtin_amdgcn_raw_buffer_load_b16(rbs, gv_rowmap_qkv(n, D, a.rope_heads) * 2, 0, 0);
-        er[B].bs[r + 1] = __builtin_amdgcn_raw_buffer_load_b16(rbs, gv_rowmap_qkv(n + 1, D, a.rope_heads) * 2, 0, 0);
+        er[B].bs[r] = __builtin_amdgcn_raw_buffer_load_b16(rbs, qk_rowmap(n, D, rope_heads) * 2, 0, 0);
+        er[B].bs[r + 1] = __builtin_amdgcn_raw_buffer_load_b16(rbs, qk_rowmap(n + 1, D, rope_heads) * 2, 0, 0);
       }
     }
   };
@@ -216,7 +210,8 @@ __global__ __launch_bounds__(512) void gv_kernel(const u32x4* __restrict__ w, co
       }
     } else {
       // GV_QKV: rows (2m, 2m+1) of a q / k head are RoPE partners (m, m + D/2) (model_utils.py:17-52, cache.py:53-65)
-      const int D = a.D, half = D / 2;
+      const QkvDst& q = a.qkv;
+      const int D = q.D;
 #pragma unroll
       for (int r = 0; r < RW; r += 2) {
         const int n = n0 + r;
@@ -225,28 +220,15 @@ __global__ __launch_bounds__(512) void gv_kernel(const u32x4* __restrict__ w, co
         asm volatile("" : "+v"(va), "+v"(vb));       // fp32 products of their own (common.h: rnd_prod)
         if (a.bias) { va += P::to_f(er[B].bs[r]); vb += P::to_f(er[B].bs[r + 1]); }
         const float a0 = rnd<P>(va), b0 = rnd<P>(vb);
-        if (head < a.Hq + a.Hkv) {
+        // slot_t is trusted here (the model runtime derives it from the engine's guarded state: HipEngine.step refuses
+        // a tree that would pass max_length); a per-store range check costs this kernel 24 B of scratch per lane
+        // (tests/test_abi.py guards that).  The stand-alone umb_kv_append is the range-checked form.
+        if (head < q.Hq + q.Hkv) {
           const float cl = P::to_f(er[B].cl[r / 2]), ch = P::to_f(er[B].ch[r / 2]);
           const float sl_ = P::to_f(er[B].sl[r / 2]), sh = P::to_f(er[B].sh[r / 2]);
-          const float lo0 = rnd<P>(mul_rnd<P>(a0, cl) - mul_rnd<P>(b0, sl_));
-          const float hi0 = rnd<P>(mul_rnd<P>(b0, ch) + mul_rnd<P>(a0, sh));
-          // slot_t is trusted here (the model runtime derives it from the engine's guarded state: HipEngine.step refuses
-          // a tree that would pass max_length); a per-store range check costs this kernel 24 B of scratch per lane
-          // (tests/test_abi.py guards that).  The stand-alone umb_kv_append is the range-checked form.
-          // q rows are row-major; the K / V^T caches are in fragment order inside a head's slab (common.h)
-          if (head < a.Hq) {
-            u16* dst = a.q_out + ((long)t * a.Hq + head) * D;
-            dst[m] = P::from_f(lo0);
-            dst[m + half] = P::from_f(hi0);
-          } else {
-            u16* dst = a.kc + (long)(head - a.Hq) * a.Lmax * D;
-            dst[kc_off(slot_t, m, D)] = P::from_f(lo0);
-            dst[kc_off(slot_t, m + half, D)] = P::from_f(hi0);
-          }
+          qk_store_pair(q, head, m, t, slot_t, rope_rotate<P>(a0, b0, cl, ch, sl_, sh));
         } else {
-          u16* dst = a.vt + (long)(head - a.Hq - a.Hkv) * D * VT_LD(a.Lmax);
-          dst[vt_off(dp, slot_t, D)] = P::from_f(a0);
-          dst[vt_off(dp + 1, slot_t, D)] = P::from_f(b0);
+          v_store2<P>(q, head, dp, dp + 1, slot_t, a0, b0);
         }
       }
     }
@@ -284,10 +266,7 @@ __global__ void repack_rows_kernel(const u32x4* __restrict__ W, u32x4* __restric
   const int n = (int)(gid / K8), c = (int)(gid % K8);
   int src = n;
   if (mode == 1) src = (n & 1) ? N / 2 + (n >> 1) : (n >> 1);
-  if (mode == 2) {
-    const int head = n / D, dp = n % D;
-    if (head < rope_heads) src = head * D + ((dp & 1) ? (dp >> 1) + D / 2 : (dp >> 1));
-  }
+  if (mode == 2) src = qk_rowmap(n, D, rope_heads);
   out[gid] = W[(long)src * K8 + c];
 }
 
@@ -340,13 +319,12 @@ extern "C" int umb_gemv(void* out, const void* x, const void* w_rows, int T, int
   a.ssq_dim = fx->ssq_dim; a.eps = fx->eps;
   a.h = (u16*)fx->h; a.hw = (u16*)fx->hw; a.norm_w = (const u16*)fx->norm_w; a.ssq_out = fx->ssq_out;
   a.ssq_out_stride = fx->ssq_out_stride;
-  a.pos = fx->pos; a.slot = fx->slot; a.cosT = (const u16*)fx->cosT; a.sinT = (const u16*)fx->sinT; a.q_out = (u16*)fx->q_out;
-  a.kc = (u16*)fx->k_cache; a.vt = (u16*)fx->vt_cache; a.bias = (const u16*)fx->bias;
-  a.Hq = fx->Hq; a.Hkv = fx->Hkv; a.D = fx->D; a.Lmax = fx->Lmax; a.rope_heads = fx->Hq + fx->Hkv;
+  a.qkv = qkv_dst(*fx); a.bias = (const u16*)fx->bias;
   if (epi == GV_RESID && (!a.h || (a.norm_w && !a.hw))) return UMB_EINVAL;
   if (epi == GV_SILU && (!out || N % 2)) return UMB_EINVAL;
-  if (epi == GV_QKV && (!a.pos || !a.slot || !a.cosT || !a.sinT || !a.q_out || !a.kc || !a.vt || a.D % 2 || N % 2)) return UMB_EINVAL;
-  if (epi == GV_QKV && (a.D % 32 || a.Lmax % 32 || a.Lmax < 32)) return UMB_EINVAL;   // fragment-ordered caches (common.h): whole 32-key / 32-feature tiles
+  const QkvDst& q = a.qkv;
+  if (epi == GV_QKV && (!q.pos || !q.slot || !q.cosT || !q.sinT || !q.q_out || !q.kc || !q.vt || q.D % 2 || N % 2)) return UMB_EINVAL;
+  if (epi == GV_QKV && (q.D % 32 || q.Lmax % 32 || q.Lmax < 32)) return UMB_EINVAL;   // fragment-ordered caches (common.h): whole 32-key / 32-feature tiles
   // the kernel reads the producer's sums of squares as <= 4 values per lane: 256 groups at most
   if (a.ssq_in && (a.ssq_groups < 1 || a.ssq_groups > 256 || a.ssq_dim <= 0.f)) return UMB_EINVAL;
   const int KS = K / 2048;

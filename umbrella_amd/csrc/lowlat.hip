@@ -35,6 +35,7 @@
 //   RESID   h += round(out); hw = h * w_next (FM); ssq_out[t][row group] = sum h^2
 #include "../../include/umbrella_hip.h"
 #include "common.h"
+#include "qkv_epilogue.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -47,8 +48,7 @@ struct LLArgs {
   int T, N, K, WN, WK, epi, row_from, round_out;
   const float* ssq_in; int ssq_groups, ssq_in_stride; float ssq_dim, eps;
   u16* h; u16* hw; const u16* norm_w; float* ssq_out; int ssq_out_stride;
-  const int* pos; const int* slot; const u16* cosT; const u16* sinT; u16* q_out; u16* kc; u16* vt; const u16* bias;
-  int Hq, Hkv, D, Lmax, rope_heads;
+  const u16* bias; QkvDst qkv;
 };
 
 template <int AWQ, int R> struct LStage {           // weights of one k-block (R n-tiles)
@@ -62,13 +62,6 @@ template <int R> struct LMeta {                       // int4: 4 x {fp16 scale, 
 // wait states are only inserted for instructions the compiler can see (an inline-asm v_and_or_b32 here produced wrong
 // columns at some ring depths).  With `magic` pinned in a VGPR the pattern still selects to one v_and_or_b32.
 __device__ __forceinline__ unsigned and_or_b32(unsigned a, unsigned mask, unsigned magic_v) { return (a & mask) | magic_v; }
-
-// packed source row of HF feature order (inverse use: bias lookup) -- same map as gemm.hip rowmap()
-__device__ __forceinline__ int ll_rowmap_qkv(int n, int D, int rope_heads) {
-  const int head = n / D, dp = n % D;
-  if (head >= rope_heads) return n;
-  return head * D + ((dp & 1) ? (dp >> 1) + D / 2 : (dp >> 1));
-}
 
 // 8 waves per block, up to 256 registers (two waves per SIMD): the operand rings want the registers more than the
 // kernel wants a second resident block -- bytes in flight per CU come from the ring depth.
@@ -353,21 +346,7 @@ __global__ __launch_bounds__(512, 2) void ll_gemm_kernel(const u32x4* __restrict
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const int n = (nt0 + r) * 16 + g * 4;
-          const long off = (long)t * N + n;
-          const uint2 hr = *reinterpret_cast<const uint2*>(a.h + off);
-          const f32x4 v = acc[r][tt];
-          const float h0 = rnd<P>(rnd<P>(v[0]) + lo_f<P>(hr.x)), h1 = rnd<P>(rnd<P>(v[1]) + hi_f<P>(hr.x));
-          const float h2v = rnd<P>(rnd<P>(v[2]) + lo_f<P>(hr.y)), h3 = rnd<P>(rnd<P>(v[3]) + hi_f<P>(hr.y));
-          uint2 o;
-          o.x = pack2<P>(h0, h1); o.y = pack2<P>(h2v, h3);
-          *reinterpret_cast<uint2*>(a.h + off) = o;
-          if (a.norm_w) {
-            const uint2 w = *reinterpret_cast<const uint2*>(a.norm_w + n);
-            uint2 ow;
-            ow.x = pack2<P>(h0 * lo_f<P>(w.x), h1 * hi_f<P>(w.x)); ow.y = pack2<P>(h2v * lo_f<P>(w.y), h3 * hi_f<P>(w.y));
-            *reinterpret_cast<uint2*>(a.hw + fm_off(t, n, TT)) = ow;
-          }
-          sq += h0 * h0 + h1 * h1 + h2v * h2v + h3 * h3;
+          sq += resid_step4<P>(acc[r][tt], a.h + (long)t * N + n, a.norm_w, n, a.hw + fm_off(t, n, TT));   // hw in FM order
         }
       }
       sq += __shfl_xor(sq, 16, 64);
@@ -378,13 +357,14 @@ __global__ __launch_bounds__(512, 2) void ll_gemm_kernel(const u32x4* __restrict
   }
   // LL_QKV: rows were permuted at load so (2m, 2m+1) of a q / k head are RoPE partners (m, m + D/2)
   {
-    const int D = a.D, half = D / 2;
+    const QkvDst& q = a.qkv;
+    const int D = q.D, half = D / 2;
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt) {
       const int t = tt * 16 + j;
       if (t >= T) continue;
-      const int sl = a.slot[t];
-      const long cb = (long)a.pos[t] * D;
+      const int sl = q.slot[t];
+      const long cb = (long)q.pos[t] * D;
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const int n = (nt0 + r) * 16 + g * 4;
@@ -392,29 +372,19 @@ __global__ __launch_bounds__(512, 2) void ll_gemm_kernel(const u32x4* __restrict
         f32x4 v = acc[r][tt] * inv[tt];
         if (a.bias) {      // F.linear(x, W, b) (qwen.py:94-96): bias joins the fp32 accumulator, one rounding
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += P::to_f(a.bias[ll_rowmap_qkv(n + e, D, a.rope_heads)]);
+          for (int e = 0; e < 4; ++e) v[e] += P::to_f(a.bias[qk_rowmap(n + e, D, q.Hq + q.Hkv)]);
         }
         const float a0 = rnd<P>(v[0]), b0 = rnd<P>(v[1]), a1 = rnd<P>(v[2]), b1 = rnd<P>(v[3]);
-        if (head < a.Hq + a.Hkv) {
-          const unsigned cl = *reinterpret_cast<const unsigned*>(a.cosT + cb + m);
-          const unsigned ch = *reinterpret_cast<const unsigned*>(a.cosT + cb + m + half);
-          const unsigned sl_ = *reinterpret_cast<const unsigned*>(a.sinT + cb + m);
-          const unsigned sh = *reinterpret_cast<const unsigned*>(a.sinT + cb + m + half);
-          // rotate-half in the model dtype: every product and the sum are rounded (eager torch, model_utils.py:50-51)
-          const float lo0 = rnd<P>(mul_rnd<P>(a0, lo_f<P>(cl)) - mul_rnd<P>(b0, lo_f<P>(sl_)));
-          const float lo1 = rnd<P>(mul_rnd<P>(a1, hi_f<P>(cl)) - mul_rnd<P>(b1, hi_f<P>(sl_)));
-          const float hi0 = rnd<P>(mul_rnd<P>(b0, lo_f<P>(ch)) + mul_rnd<P>(a0, lo_f<P>(sh)));
-          const float hi1 = rnd<P>(mul_rnd<P>(b1, hi_f<P>(ch)) + mul_rnd<P>(a1, hi_f<P>(sh)));
-          // q rows are row-major; the K / V^T caches are in fragment order inside a head's slab (common.h; m is even)
-          u16* dlo = (head < a.Hq) ? a.q_out + ((long)t * a.Hq + head) * D + m
-                                   : a.kc + (long)(head - a.Hq) * a.Lmax * D + kc_off(sl, m, D);
-          u16* dhi = (head < a.Hq) ? dlo + half : a.kc + (long)(head - a.Hq) * a.Lmax * D + kc_off(sl, m + half, D);
-          *reinterpret_cast<unsigned*>(dlo) = pack2<P>(lo0, lo1);
-          *reinterpret_cast<unsigned*>(dhi) = pack2<P>(hi0, hi1);
+        if (head < q.Hq + q.Hkv) {
+          const unsigned cl = *reinterpret_cast<const unsigned*>(q.cosT + cb + m);
+          const unsigned ch = *reinterpret_cast<const unsigned*>(q.cosT + cb + m + half);
+          const unsigned sl_ = *reinterpret_cast<const unsigned*>(q.sinT + cb + m);
+          const unsigned sh = *reinterpret_cast<const unsigned*>(q.sinT + cb + m + half);
+          const u16 lo0 = rope_lo<P>(a0, b0, lo_f<P>(cl), lo_f<P>(sl_)), lo1 = rope_lo<P>(a1, b1, hi_f<P>(cl), hi_f<P>(sl_));
+          const u16 hi0 = rope_hi<P>(a0, b0, lo_f<P>(ch), lo_f<P>(sh)), hi1 = rope_hi<P>(a1, b1, hi_f<P>(ch), hi_f<P>(sh));
+          qk_store_pairs2(q, head, m, t, sl, lo0, lo1, hi0, hi1);
         } else {
-          u16* vb = a.vt + (long)(head - a.Hq - a.Hkv) * D * VT_LD(a.Lmax);
-          vb[vt_off(dp, sl, D)] = P::from_f(a0); vb[vt_off(dp + 1, sl, D)] = P::from_f(b0);
-          vb[vt_off(dp + 2, sl, D)] = P::from_f(a1); vb[vt_off(dp + 3, sl, D)] = P::from_f(b1);
+          v_store4<P>(q, head, dp, sl, a0, b0, a1, b1);
         }
       }
     }
@@ -516,16 +486,15 @@ extern "C" int umb_gemm_ll(void* out, const void* x_fm, const void* wpacked, con
     a.ssq_dim = fx->ssq_dim; a.eps = fx->eps;
     a.h = (u16*)fx->h; a.hw = (u16*)fx->hw; a.norm_w = (const u16*)fx->norm_w; a.ssq_out = fx->ssq_out;
     a.ssq_out_stride = fx->ssq_out_stride;
-    a.pos = fx->pos; a.slot = fx->slot; a.cosT = (const u16*)fx->cosT; a.sinT = (const u16*)fx->sinT;
-    a.q_out = (u16*)fx->q_out; a.kc = (u16*)fx->k_cache; a.vt = (u16*)fx->vt_cache; a.bias = (const u16*)fx->bias;
-    a.Hq = fx->Hq; a.Hkv = fx->Hkv; a.D = fx->D; a.Lmax = fx->Lmax; a.rope_heads = fx->Hq + fx->Hkv;
+    a.qkv = qkv_dst(*fx); a.bias = (const u16*)fx->bias;
   }
   if (a.row_from < 0 || a.row_from >= T) return UMB_EINVAL;
   if (a.ssq_in && (a.ssq_groups < 1 || a.ssq_in_stride < a.ssq_groups || a.ssq_dim <= 0.f)) return UMB_EINVAL;
   if (epi == LL_RESID && (!a.h || (a.norm_w && !a.hw) || (a.ssq_out && a.ssq_out_stride < N / 16 / R))) return UMB_EINVAL;
-  if (epi == LL_QKV && (!a.pos || !a.slot || !a.q_out || !a.kc || !a.vt || !a.cosT || !a.sinT || a.D % 4 ||
-                        N != (a.Hq + 2 * a.Hkv) * a.D)) return UMB_EINVAL;
-  if (epi == LL_QKV && (a.D % 32 || a.Lmax % 32 || a.Lmax < 32)) return UMB_EINVAL;   // fragment-ordered caches: whole tiles
+  const QkvDst& q = a.qkv;
+  if (epi == LL_QKV && (!q.pos || !q.slot || !q.q_out || !q.kc || !q.vt || !q.cosT || !q.sinT || q.D % 4 ||
+                        N != (q.Hq + 2 * q.Hkv) * q.D)) return UMB_EINVAL;
+  if (epi == LL_QKV && (q.D % 32 || q.Lmax % 32 || q.Lmax < 32)) return UMB_EINVAL;   // fragment-ordered caches: whole tiles
   if (epi == LL_SILU && N % 32) return UMB_EINVAL;
   const int TT = ll_tt(T);
   auto run = [&](auto tag) -> int {

@@ -121,10 +121,15 @@ static inline void rms_from_ssq(UmbGemmFused& f, const UmbModel* m, const UmbWor
 static inline void rms_from_ssq(UmbGemmLL& f, const UmbModel* m, const UmbWorkspace* ws, int groups) {
   f.ssq_in = ws->ssq; f.ssq_groups = groups; f.ssq_in_stride = ws->ssq_stride; f.ssq_dim = (float)m->H; f.eps = m->eps;
 }
-// epi 3 of the low-latency / GEMV kernels: (+bias), RoPE at the tree positions, q out, K / V appended at their slots
-static inline void qkv_epilogue(UmbGemmLL& f, const UmbModel* m, const UmbWorkspace* ws, const KV& kv, const void* bias) {
+// the q/k/v epilogue's destinations in any family's argument struct (UmbGemmFused, UmbGemmLL, UmbChain: the same member names):
+// RoPE at the tree positions, q out, K / V appended at their slots
+template <typename F> static inline void qkv_dest(F& f, const UmbModel* m, const UmbWorkspace* ws, const KV& kv) {
   f.pos = ws->pos; f.slot = ws->slot; f.cosT = m->rope_cos; f.sinT = m->rope_sin; f.q_out = ws->q; f.k_cache = kv.k;
-  f.vt_cache = kv.vt; f.bias = bias; f.Hq = m->Hq; f.Hkv = m->Hkv; f.D = m->D; f.Lmax = m->Lmax;
+  f.vt_cache = kv.vt; f.Hq = m->Hq; f.Hkv = m->Hkv; f.D = m->D; f.Lmax = m->Lmax;
+}
+// epi 3 of the low-latency / GEMV kernels: (+bias)
+static inline void qkv_epilogue(UmbGemmLL& f, const UmbModel* m, const UmbWorkspace* ws, const KV& kv, const void* bias) {
+  qkv_dest(f, m, ws, kv); f.bias = bias;
 }
 // epi 4 of the same: h += out ; hw = h * norm_w ; sums of squares
 static inline void resid_epilogue(UmbGemmLL& f, const UmbWorkspace* ws, const void* norm_w) {
@@ -269,8 +274,7 @@ static int layer_fused(const UmbModel* m, const UmbWorkspace* ws, const UmbStep*
   // 1. qkv GEMM -> (last split block) 1/rms, RoPE at tree positions, q out, K/V appended at their slots
   rms_from_ssq(fx, m, ws, ws->ssq_stride, 0);
   fx.counters = ws->counters;
-  fx.pos = ws->pos; fx.slot = ws->slot; fx.cosT = m->rope_cos; fx.sinT = m->rope_sin;
-  fx.q_out = ws->q; fx.k_cache = kv.k; fx.vt_cache = kv.vt; fx.Hq = m->Hq; fx.Hkv = m->Hkv; fx.D = m->D; fx.Lmax = m->Lmax;
+  qkv_dest(fx, m, ws, kv);
   CK(lin(ly.qkv, ws->hw, m->H, ws->partial, T, dt, st, /*EPI_QKV*/3, &fx));
   // 2. tree attention (+ fused split merge)
   CK(tree_attn(m, ws, s, kv, -1, st));
@@ -474,15 +478,13 @@ static int chain_launch(const UmbModel* m, const UmbWorkspace* ws, const UmbStep
   if (lt >= 0) {
     const UmbLayer& ly = m->layers[lt];
     c.tail = 1; c.w_qkv = ly.qkv.w_rows;
-    const KV kv = kv_slabs(m, lt);
-    c.k_cache = kv.k; c.vt_cache = kv.vt;
-    c.pos = ws->pos; c.slot = ws->slot; c.cosT = m->rope_cos; c.sinT = m->rope_sin; c.q_out = ws->q;
+    qkv_dest(c, m, ws, kv_slabs(m, lt));
   }
   c.NQKV = m->layers[lt >= 0 ? lt : lf].qkv.N;
   c.h = ws->h; c.hw = ws->hw; c.ssq = ws->ssq; c.next_norm = next_norm; c.xchg = ws->chain_xchg;
   c.T = s->T; c.Tmax = UMB_CHAIN_TMAX;       /* the exchange layout is fixed (umbrella_hip.h: UmbWorkspace.chain_xchg) */
   c.H = m->H; c.I = m->I; c.ssq_stride = ws->ssq_stride; c.ssq_groups_in = groups_in;
-  c.Hq = m->Hq; c.Hkv = m->Hkv; c.D = m->D; c.Lmax = m->Lmax; c.eps = m->eps;
+  c.Hq = m->Hq; c.Hkv = m->Hkv; c.D = m->D; c.Lmax = m->Lmax; c.eps = m->eps;   // shapes: a front-only launch is checked against them too
   return umb_draft_chain(&c, m->dtype, st);
 }
 // the chain's layers and head, behind the GEMV prologue.  2 launches per layer: the first q/k/v alone, then per layer tree
